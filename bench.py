@@ -6,12 +6,17 @@ encoder features already resident in HBM: 8 fused 3x3 MFMA convolutions, 9 wavel
 -> 4 disparity maps + 16 coefficient planes.  N GPUs = N independent shards of the batch dimension
 (weak scaling; the forward path has no exchange step, so no collective is issued).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: re-executes itself under torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                  (N > 1: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`, plus `train`: the
-data-parallel TRAINING step of BASELINE.json configs[2] (KITTI ResNet50 1024x320, batch 8 per GPU) through the RCCL
-gradient exchange -- frames/s, gradient bytes, exposed all-reduce time, RCCL world size (skipped with --no-train).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline figure needs:
+set-up, warm-up, the K timed steps, the line.  --dump-outputs DIR writes the output maps of the last timed step (rank 0)
+as DIR/<name>.npy, float32, so that two builds can be compared output for output.  --full adds the extras: the per-kernel
+`roofline` pass, the per-step spread, the eager and static-input timings, `cpu_baseline` (the CPU oracle, also the parity
+check of the timed mode; --no-cpu-baseline skips it), the 1024x320 forward and `train`: the data-parallel TRAINING step
+of BASELINE.json configs[2] (KITTI ResNet50 1024x320, batch 8 per GPU) through the RCCL gradient exchange -- frames/s,
+gradient bytes, exposed all-reduce time, RCCL world size (skipped with --no-train).
 Other workloads for the record: --workload train (configs[2] alone), --workload train-nyu (configs[4]: NYUv2
 DenseNet161 640x480 batch 4 per GPU).
 """
@@ -46,6 +51,18 @@ def build_model(dev):
     dec.enable_graph(os.environ.get("WMD_BENCH_GRAPH", "1") != "0")
     feats = [torch.from_numpy(f).to(dev) for f in synth.encoder_features(BATCH, HEIGHT, WIDTH, R18, seed=1)]
     return dec, feats
+
+
+def dump_outputs(out, path, limit=64 << 20):
+    """The output dict of the last timed step -> path/<name>.npy, float32, every map in full: ("disp", 0) -> disp_0.npy,
+    ("wavelets", 2, "LH") -> wavelets_2_LH.npy (4 disparity maps + 16 coefficient planes, 15 MB at batch 12 640x192)."""
+    arrays = {"_".join(str(p) for p in k): v.detach().float().cpu().numpy() for k, v in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit("bench.py: the outputs take %d bytes, more than the %d a dump may hold" % (total, limit))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(dec, feats, gpu_out=None, budget_s=20.0):
@@ -432,6 +449,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="also the extras of the fwd line (roofline pass, per-step spread, eager and "
+                    "static-input timings, CPU baseline, 1024x320 forward, training steps); off: the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output maps of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the secondary workloads of the fwd line (1024x320 forward, training steps)")
     ap.add_argument("--no-train-nyu", action="store_true", help="skip the NYUv2 DenseNet161 training step of the fwd line")
@@ -450,6 +470,10 @@ def main():
     ap.add_argument("--train-steps", type=int, default=30)
     ap.add_argument("--exchange-backend", choices=["rccl", "torch"], default=os.environ.get("WMD_BENCH_EXCHANGE", "rccl"))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "fwd":
+        ap.error("--dump-outputs writes the outputs of the fwd workload only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -507,21 +531,24 @@ def main():
     # its steady clocks (tools/probes/bench_protocol_probe.py: first steps 0.625 ms against 0.565 steady; K = 20 after an idle
     # gap 0.603 ms/step, without 0.565).  Round 4 ran the eager per-kernel pass first and let the first warm-up step capture
     # the graphs: that put the capture's idle gap directly in front of the timed replays (driver protocol 0.607 ms/step on a box
-    # whose 50-step loop read 0.575).  So: (1) set-up, which includes the graph capture; (2) the per-kernel roofline pass -- K
-    # eager steps with a hipEvent pair around every launch, needed anyway, and 12+ ms of GPU work -- with the captured graphs
-    # kept (decoder.eager()); (3) directly behind it the W warm-up steps, which are replays like the timed ones; (4) the timed
-    # region: EXACTLY K steps between barrier + synchronize, nothing but the K forward calls inside.  The per-step spread (p10 /
-    # median / p90) comes from one more K-step pass with an event after every step, outside the timed region.
+    # whose 50-step loop read 0.575).  So: (1) set-up, which includes the graph capture and a burst of replays; (2) with --full,
+    # the per-kernel roofline pass -- K eager steps with a hipEvent pair around every launch, 12+ ms of GPU work -- with the
+    # captured graphs kept (decoder.eager()); (3) directly behind it the W warm-up steps, which are replays like the timed ones;
+    # (4) the timed region: EXACTLY K steps between barrier + synchronize, nothing but the K forward calls inside.  With --full
+    # the per-step spread (p10 / median / p90) comes from one more K-step pass with an event after every step, outside the
+    # timed region.
     graph_on = os.environ.get("WMD_BENCH_GRAPH", "1") != "0"
     dec.enable_graph(graph_on)
     with torch.no_grad():
         dec(feats)                              # set-up: tunes what the committed choices do not cover, captures the graphs
-        for _ in range(30):                     # ... and 17 ms of replays bring the clocks back up before the per-kernel pass,
-            dec(feats)                          #     whose launch durations are what `roofline` reports
-    roof = roofline(dec, feats, args.steps)     # every rank runs it (same state on every GPU); rank 0's goes into the line
+        for _ in range(30):                     # ... and 17 ms of replays bring the clocks back up before the per-kernel pass
+            dec(feats)                          #     (whose launch durations are what `roofline` reports) or the warm-up
+    # every rank runs the roofline pass (same state on every GPU); rank 0's goes into the line
+    roof = roofline(dec, feats, args.steps) if args.full else None
+    profiled = args.steps + 1 if args.full else 0
     warm_eff = {"capture_setup_eager_forwards": 2 if graph_on else 1, "graph_replays_before_profile_pass": 31 if graph_on else 30,
-                "eager_profiled_forwards": args.steps + 1, "declared_warmup_replays": args.warmup,
-                "total_forwards_before_timer": (33 if graph_on else 31) + args.steps + 1 + args.warmup}
+                "eager_profiled_forwards": profiled, "declared_warmup_replays": args.warmup,
+                "total_forwards_before_timer": (33 if graph_on else 31) + profiled + args.warmup}
     with torch.no_grad():
         for _ in range(args.warmup):
             dec(feats)
@@ -531,66 +558,73 @@ def main():
             out = dec(feats)
         barrier()
         elapsed = time.perf_counter() - t0
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step spread (extra fields only)
-        marks[0].record()
-        for k in range(args.steps):
-            out = dec(feats)
-            marks[k + 1].record()
-        torch.cuda.synchronize()
-        step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
+        # what the last timed step handed back (graph replays write into the same output buffers every step)
+        last = {k: v.detach().clone() for k, v in out.items()} if rank == 0 and (args.dump_outputs or args.full) else None
+        if args.full:
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step spread (extra fields only)
+            marks[0].record()
+            for k in range(args.steps):
+                out = dec(feats)
+                marks[k + 1].record()
+            torch.cuda.synchronize()
+            step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     if world > 1:
         tt = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert all(torch.isfinite(v).all() for v in out.values())
-    checked = {k: v.detach().clone() for k, v in out.items()} if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
-    # Beside the headline (replay keyed on the identity of the resident feature tensors): the eager wall-clock per step (python
-    # launches, no graph) and the static-input entry -- a caller whose encoder hands over FRESH tensors every step copies them into
-    # decoder-owned buffers (decoder.bind_inputs) and replays the one capture; the copies (167.7 MB per batch) are inside the figure.
-    with torch.no_grad():
-        dec.enable_graph(False)
-        for _ in range(3):
-            dec(feats)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            out = dec(feats)
-        torch.cuda.synchronize()
-        eager_ms = (time.perf_counter() - t0) / args.steps * 1e3
-        # static-input hand-overs (decoder.bind_inputs).  "Fresh tensors every step" is emulated by two pre-made
-        # feature sets handed over alternately -- the recurring addresses a caching allocator in steady state returns; producing
-        # them is the encoder's work and stays outside the figure.
-        fresh = [[f.clone() for f in feats] for _ in range(2)]
-
-        def bound_loop(call):
-            for k in range(6):
-                call(k)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    checked = last if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    if args.full:
+        # Beside the headline (replay keyed on the identity of the resident feature tensors): the eager wall-clock per step (python
+        # launches, no graph) and the static-input entry -- a caller whose encoder hands over FRESH tensors every step copies them
+        # into decoder-owned buffers (decoder.bind_inputs) and replays the one capture; the copies (167.7 MB per batch) are inside
+        # the figure.
+        with torch.no_grad():
+            dec.enable_graph(False)
+            for _ in range(3):
+                dec(feats)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for k in range(args.steps):
-                call(k)
+            for _ in range(args.steps):
+                out = dec(feats)
             torch.cuda.synchronize()
-            return (time.perf_counter() - t0) / args.steps * 1e3
+            eager_ms = (time.perf_counter() - t0) / args.steps * 1e3
+            # static-input hand-overs (decoder.bind_inputs).  "Fresh tensors every step" is emulated by two pre-made
+            # feature sets handed over alternately -- the recurring addresses a caching allocator in steady state returns; producing
+            # them is the encoder's work and stays outside the figure.
+            fresh = [[f.clone() for f in feats] for _ in range(2)]
 
-        dec.bind_inputs(feats, pointer_sets=0)                       # route 3 only: copy into decoder-owned buffers (rounds 3-5)
-        caps = dec.capture_count
-        copy_ms = bound_loop(lambda k: dec(fresh[k & 1]))
-        copy_recaptures = dec.capture_count - caps
-        dec.enable_graph(False)
-        dec.bind_inputs(feats)                                       # default: recurring address sets get a capture of their own
-        caps = dec.capture_count
-        bound_ms = bound_loop(lambda k: dec(fresh[k & 1]))
-        recaptures = dec.capture_count - caps
-        routes = dict(dec.static_route)
-        dec.enable_graph(False)
-        dec.bind_inputs(fresh[0], adopt=True)                        # the caller's tensors ARE the graph's input buffers
-        adopt_ms = bound_loop(lambda k: dec(fresh[0]))
-        dec.enable_graph(False)
-        del fresh
+            def bound_loop(call):
+                for k in range(6):
+                    call(k)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(args.steps):
+                    call(k)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.steps * 1e3
+
+            dec.bind_inputs(feats, pointer_sets=0)                       # route 3 only: copy into decoder-owned buffers (rounds 3-5)
+            caps = dec.capture_count
+            copy_ms = bound_loop(lambda k: dec(fresh[k & 1]))
+            copy_recaptures = dec.capture_count - caps
+            dec.enable_graph(False)
+            dec.bind_inputs(feats)                                       # default: recurring address sets get a capture of their own
+            caps = dec.capture_count
+            bound_ms = bound_loop(lambda k: dec(fresh[k & 1]))
+            recaptures = dec.capture_count - caps
+            routes = dict(dec.static_route)
+            dec.enable_graph(False)
+            dec.bind_inputs(fresh[0], adopt=True)                        # the caller's tensors ARE the graph's input buffers
+            adopt_ms = bound_loop(lambda k: dec(fresh[0]))
+            dec.enable_graph(False)
+            del fresh
 
     # north_star's second resolution: the dense decoder forward at KITTI ResNet50 1024x320, batch 8 (configs[2]'s shapes)
     fwd_1024 = None
-    if not args.no_train and rank == 0:
+    if args.full and not args.no_train and rank == 0:
         try:
             fwd_1024 = forward_extra(dev, [64, 256, 512, 1024, 2048], 8, 320, 1024, args.steps,
                                      "KITTI ResNet50 1024x320 dense wavelet decoder + IDWT, forward, batch 8, hipGraph replay")
@@ -606,23 +640,10 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             # forwards executed on the device before the timer starts, by kind (VERDICT r5 #7 / ADVICE r5: the declared --warmup
-            # replays are the LAST of them; the set-up and the per-kernel roofline pass run before, so the timed region starts at
-            # steady clocks -- the figure is a steady-state rate, like-for-like with r05, not with r01-r04's cold protocol)
+            # replays are the LAST of them; the set-up (and with --full the per-kernel roofline pass) run before, so the timed region
+            # starts at steady clocks -- the figure is a steady-state rate, like-for-like with r05, not with r01-r04's cold protocol)
             "warmup_effective": warm_eff,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "ms_per_step_p10_median_p90": [round(step_ms[int(q * (len(step_ms) - 1))], 4) for q in (0.1, 0.5, 0.9)],
-            "eager_ms_per_step": round(eager_ms, 4),
-            "static_input_ms_per_step": {"value": round(bound_ms, 4), "captures_for_recurring_address_sets": recaptures, "routes": routes,
-                                         "copy_route_ms_per_step": round(copy_ms, 4), "copy_route_recaptures": copy_recaptures,
-                                         "adopted_buffers_ms_per_step": round(adopt_ms, 4),
-                                         "what": "decoder.bind_inputs: feature tensors that are NOT the captured ones every step (two address sets "
-                                                 "alternating = a caching allocator in steady state). value: default route -- one capture per "
-                                                 "recurring address set (second sighting, <= 4 sets, inputs not retained), then replayed in place, "
-                                                 "no copy; copy_route: pointer_sets=0, every step copies 167.7 MB into decoder-owned buffers "
-                                                 "(rounds 3-5's figure); adopted_buffers: bind_inputs(adopt=True) / decoder.input_buffers(), the "
-                                                 "producer writes into the graph's own input buffers. The config-3 training step (trainer.py:"
-                                                 "240-241) runs the decoder eagerly under autograd on the encoder's output tensors in place: "
-                                                 "no graph, no copy (train.decoder_ms)"},
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -631,17 +652,33 @@ def main():
             "config": {"workload": "KITTI ResNet18 640x192 dense wavelet decoder + 4x Haar IDWT, forward, batch 12 per GPU "
                                    "(BASELINE.json configs[1]); encoder features resident in HBM",
                        "batch_per_gpu": BATCH, "global_batch": BATCH * world, "parallelism": "dp%d (independent shards)" % world},
-            "roofline": roof,
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(dec, feats, checked),   # rank 0, N=1 only
-            "fwd_1024x320": fwd_1024,
-            "train": None,
-            "train_strong": None,
-            "train_nyu": None,
         }
+        if args.full:
+            res.update({
+                "ms_per_step_p10_median_p90": [round(step_ms[int(q * (len(step_ms) - 1))], 4) for q in (0.1, 0.5, 0.9)],
+                "eager_ms_per_step": round(eager_ms, 4),
+                "static_input_ms_per_step": {"value": round(bound_ms, 4), "captures_for_recurring_address_sets": recaptures, "routes": routes,
+                                             "copy_route_ms_per_step": round(copy_ms, 4), "copy_route_recaptures": copy_recaptures,
+                                             "adopted_buffers_ms_per_step": round(adopt_ms, 4),
+                                             "what": "decoder.bind_inputs: feature tensors that are NOT the captured ones every step (two address "
+                                                     "sets alternating = a caching allocator in steady state). value: default route -- one capture "
+                                                     "per recurring address set (second sighting, <= 4 sets, inputs not retained), then replayed in "
+                                                     "place, no copy; copy_route: pointer_sets=0, every step copies 167.7 MB into decoder-owned "
+                                                     "buffers (rounds 3-5's figure); adopted_buffers: bind_inputs(adopt=True) / "
+                                                     "decoder.input_buffers(), the producer writes into the graph's own input buffers. The config-3 "
+                                                     "training step (trainer.py:240-241) runs the decoder eagerly under autograd on the encoder's "
+                                                     "output tensors in place: no graph, no copy (train.decoder_ms)"},
+                "roofline": roof,
+                "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(dec, feats, checked),   # rank 0, N=1 only
+                "fwd_1024x320": fwd_1024,
+                "train": None,
+                "train_strong": None,
+                "train_nyu": None,
+            })
         _EMERGENCY["line"] = res     # what rank 0 still prints if a multi-rank training extra hangs in its set-up (Deadline)
     # data-parallel training step (BASELINE.json configs[2]) through the gradient exchange: every rank takes part
     train = train_strong = train_nyu = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         del out
         dec.enable_graph(False)
         try:      # an extra of the line: a failure here (e.g. the RCCL exchange cannot be set up) must not cost the headline figure
@@ -660,7 +697,8 @@ def main():
                 train_nyu = {"error": repr(e)[:400]}
 
     if rank == 0:
-        res.update({"train": train, "train_strong": train_strong, "train_nyu": train_nyu})
+        if args.full:
+            res.update({"train": train, "train_strong": train_strong, "train_nyu": train_nyu})
         print(json.dumps(res))
     if world > 1:
         barrier()

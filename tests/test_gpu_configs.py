@@ -429,7 +429,7 @@ def test_bench_two_rank_launch_contract_rehearsal(dev):
     JSON line from rank 0 -- runs end to end."""
     import json
     env = dict(os.environ, WMD_BENCH_BACKEND="gloo", WMD_BENCH_SHARE_DEVICES="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--train-steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--train-steps", "3",
            "--exchange-backend", "torch", "--num-layers", "18", "--height", "96", "--width", "320", "--batch", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -444,3 +444,31 @@ def test_bench_two_rank_launch_contract_rehearsal(dev):
         assert tr["n_gpus"] == 2 and tr["exchange_world_size"] == 2 and tr["config"]["batch_per_gpu"] == per_gpu
         assert tr["gradient_bytes"] > 40e6 and len(tr["ms_per_step_p10_median_p90"]) == 3
         assert tr["encoder_ms"] > 0 and tr["decoder_ms"] > 0
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_timed_step(dev, tmp_path):
+    """A plain `bench.py` run prints the headline line alone (the extras are behind --full); --dump-outputs writes the 20 maps
+    of the last timed step as float32 .npy files, which the oracle reproduces on two frames within north_star's 1e-4."""
+    import json
+    from wavelet_monodepth_amd.kitti import DepthWaveProgressiveDecoder
+    out_dir = os.path.join(str(tmp_path), "outputs")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", out_dir]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["unit"] == "frames/s" and res["dtype"] == "f32" and res["higher_is_better"]
+    assert res["ms_per_step"] > 0 and abs(res["value"] - 12e3 / res["ms_per_step"]) <= 1e-3 * res["value"]
+    assert not {"roofline", "cpu_baseline", "fwd_1024x320", "train", "train_nyu"} & set(res), sorted(res)
+    dec = synth.fill_state_dict(DepthWaveProgressiveDecoder(np.array(R18)), seed=1)
+    sd = dec.state_dict()
+    feats = kitti_feats(12, 192, 640)
+    with torch.no_grad():
+        for fr in (0, 11):
+            ref = R.kitti_wave_decoder([f[fr:fr + 1] for f in feats], sd)
+            assert len(os.listdir(out_dir)) == len(ref) == 20
+            for k, v in ref.items():
+                got = np.load(os.path.join(out_dir, "_".join(str(p) for p in k) + ".npy"))
+                assert got.dtype == np.float32 and got.shape == (12,) + tuple(v.shape[1:]), key_str(k)
+                assert_close(got[fr:fr + 1], v, NET_TOL, "frame %d %s" % (fr, key_str(k)))

@@ -708,6 +708,20 @@ def test_bench_deadline_reports_and_leaves_when_the_status_exchange_hangs():
     bench._EMERGENCY["line"] = None
 
 
+def test_bench_dump_outputs_names_the_maps_and_keeps_the_size_bound(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output map, named after its key; more than the bound is refused whole."""
+    import os, torch
+    bench = _load_bench()
+    out = {("disp", 0): torch.arange(6, dtype=torch.float64).reshape(1, 1, 2, 3), ("wavelets", 2, "LH"): torch.ones(1, 1, 1, 1)}
+    bench.dump_outputs(out, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == ["disp_0.npy", "wavelets_2_LH.npy"]
+    a = np.load(tmp_path / "d" / "disp_0.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 1, 2, 3) and np.array_equal(a.reshape(-1), np.arange(6))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(out, str(tmp_path / "e"), limit=20)
+    assert not os.path.exists(tmp_path / "e")
+
+
 def test_list_tile_query_agrees_with_the_planner_table():
     """wmd_conv_list_tile_supported (what sparse_decoder.tile_for asks) and plan_conv's work-list filter are ONE
     predicate now; the two shapes with LIST instantiations must be reported, others not."""

@@ -16,14 +16,14 @@ tests)
     tail -n 25 $OUT/pytest_gpu.log ;;
 bench)
     [ -f $OUT/tune_cache.json ] && export WMD_TUNE_CACHE=$OUT/tune_cache.json
-    timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+    timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
     tail -c 1500 $OUT/bench.json; tail -n 5 $OUT/bench.err ;;
 retune)
-    WMD_BENCH_RETUNE=1 WMD_TUNE_CACHE=$OUT/tune_cache.json timeout 900 python bench.py > $OUT/bench_retune.json 2> $OUT/bench_retune.err
+    WMD_BENCH_RETUNE=1 WMD_TUNE_CACHE=$OUT/tune_cache.json timeout 900 python bench.py --full > $OUT/bench_retune.json 2> $OUT/bench_retune.err
     tail -c 600 $OUT/bench_retune.json ;;
 stats)
     [ -f $OUT/tune_cache.json ] && export WMD_TUNE_CACHE=$OUT/tune_cache.json
-    (cd /tmp && WMD_TWO_STREAM_GRAPHS=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $REPO/bench.py --no-cpu-baseline --no-train > $OUT/stats.log 2>&1) ;;
+    (cd /tmp && WMD_TWO_STREAM_GRAPHS=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $REPO/bench.py --full --no-cpu-baseline --no-train > $OUT/stats.log 2>&1) ;;
 pmc)
     [ -f $OUT/tune_cache.json ] && export WMD_TUNE_CACHE=$OUT/tune_cache.json
     (cd /tmp && rocprofv3 -L > $OUT/counters_list.txt 2>&1)
@@ -43,7 +43,7 @@ PY
     cat $OUT/pmc_passes.txt
     while read name counters; do
         [ -z "$counters" ] && continue
-        (cd /tmp && WMD_BENCH_GRAPH=0 timeout 300 rocprofv3 --pmc $counters --output-format csv -d $OUT/pmc_$name -- python $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-train > $OUT/pmc_$name.log 2>&1)
+        (cd /tmp && WMD_BENCH_GRAPH=0 timeout 300 rocprofv3 --pmc $counters --output-format csv -d $OUT/pmc_$name -- python $REPO/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-train > $OUT/pmc_$name.log 2>&1)
         python tools/pmc_summary.py "$OUT/pmc_$name/*/*counter_collection.csv" conv_wino > $OUT/pmc_${name}_wino.txt 2>&1
     done < $OUT/pmc_passes.txt
     head -n 40 $OUT/pmc_time_wino.txt ;;
@@ -52,7 +52,7 @@ traffic)
     for pass in "fetch FETCH_SIZE" "write WRITE_SIZE"; do
         set -- $pass
         name=$1; shift
-        (cd /tmp && WMD_BENCH_GRAPH=0 timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/pmc_$name -- python $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-train > $OUT/pmc_$name.log 2>&1)
+        (cd /tmp && WMD_BENCH_GRAPH=0 timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/pmc_$name -- python $REPO/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-train > $OUT/pmc_$name.log 2>&1)
     done ;;
 esac
 done

@@ -117,7 +117,7 @@ copy("gpu_tests.txt", tag + "_gpu_tests.txt")
 method = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc <SQ counters> GRBM_GUI_ACTIVE in separate passes (tools/profile_session.sh); "
           "per-launch averages; HBM-side bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (FETCH_SIZE reports half of the fetched bytes on gfx950)")
 layers, fwd_kernels = {}, {}
-for kind, what in (("fwd", "WMD_BENCH_GRAPH=0 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-train"),
+for kind, what in (("fwd", "WMD_BENCH_GRAPH=0 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-train"),
                    ("fwd1024", "WMD_BENCH_GRAPH=0 python bench.py --workload fwd-1024 --steps 3 (KITTI ResNet50 1024x320, batch 8, forward)"),
                    ("bwd", "python tools/train_profile.py (decoder forward + backward, config 2 shapes)"),
                    ("sparse", "python tools/sparse_profile.py 0.15 (sparse KITTI decoder, batch 1)")):

@@ -22,17 +22,17 @@ pmc_passes() {   # $1 = name prefix, rest = command: FETCH_SIZE / WRITE_SIZE / S
 for w in $WHAT; do
 case $w in
 retune)   # regenerate the committed tile / split-K choices (every workload bench.py touches): profiles/<tag>_tune_cache.json
-    WMD_BENCH_RETUNE=1 WMD_TUNE_CACHE=$OUT/tune_cache.json timeout 1500 python bench.py --no-cpu-baseline > $OUT/bench_retune.json 2> $OUT/bench_retune.err
+    WMD_BENCH_RETUNE=1 WMD_TUNE_CACHE=$OUT/tune_cache.json timeout 1500 python bench.py --full --no-cpu-baseline > $OUT/bench_retune.json 2> $OUT/bench_retune.err
     tail -c 300 $OUT/bench_retune.json; echo; python -c "import json; print(len(json.load(open('$OUT/tune_cache.json'))), 'tuned keys')" ;;
 fwd)
     [ -f $OUT/tune_cache.json ] && cp $OUT/tune_cache.json profiles/${TAG}_tune_cache.json     # this session's retune, if any
-    python bench.py > $OUT/bench.json 2> $OUT/bench.err
+    python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
     # the trunk layers' problem signatures with the kernel + grid each ran on (joins the counters to layers, not to grid sizes)
-    WMD_CONV_VERBOSE=1 WMD_BENCH_GRAPH=0 python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-train 2>&1 >/dev/null | grep "sig conv" | sort -u > $OUT/conv_plan.txt
+    WMD_CONV_VERBOSE=1 WMD_BENCH_GRAPH=0 python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-train 2>&1 >/dev/null | grep "sig conv" | sort -u > $OUT/conv_plan.txt
     tail -c 400 $OUT/bench.json; echo
-    (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $REPO/bench.py --no-cpu-baseline --no-train > $OUT/stats.log 2>&1)
+    (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $REPO/bench.py --full --no-cpu-baseline --no-train > $OUT/stats.log 2>&1)
     cp $OUT/stats/*/*kernel_stats.csv $OUT/kernel_stats.csv; rm -rf $OUT/stats
-    WMD_BENCH_GRAPH=0 pmc_passes fwd python $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-train
+    WMD_BENCH_GRAPH=0 pmc_passes fwd python $REPO/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-train
     # north_star's second resolution (KITTI ResNet50 1024x320, batch 8): plan dump + the same three counter passes
     WMD_CONV_VERBOSE=1 WMD_BENCH_GRAPH=0 python bench.py --workload fwd-1024 --steps 1 2>&1 >/dev/null | grep "sig conv" | sort -u > $OUT/conv_plan_1024.txt
     WMD_BENCH_GRAPH=0 pmc_passes fwd1024 python $REPO/bench.py --workload fwd-1024 --steps 3 ;;
