@@ -243,7 +243,8 @@ typedef struct {
     float* workspace;
     size_t workspace_floats;
     int tune_cfg;       /* 0 = library model; k > 0 forces entry k-1 of the Winograd F(2x2,3x3) weight-gradient table
-                           (wmd_conv_wgrad_num_configs / _config_name; 3x3 only); -1 = direct kernel, library's tile */
+                           (wmd_conv_wgrad_num_configs / _config_name); -1 = direct kernel, library's tile.  k > num_configs,
+                           k < -1, or k > 0 with ksize != 3 is refused (WMD_ERR_UNSUPPORTED; workspace_floats returns 0)   */
     int tune_nsplit;    /* 0 = library model; > 0 forces the number of pixel-tile slices (= partial sums)          */
 } wmd_conv_wgrad_args;
 

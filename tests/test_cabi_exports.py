@@ -52,6 +52,44 @@ def test_argument_validation_without_gpu(lib):
     assert lib.wmd_conv_packed_weight_floats(32, 96, 3) == 2 * 24 * 9 * 64
 
 
+@pytest.mark.parametrize("ksize,up,C2,cfg", [(3, 1, 0, 0), (3, 2, 8, 0), (3, 1, 0, -1), (3, 2, 8, 1), (3, 1, 0, "last"),
+                                             (1, 1, 0, 0), (1, 1, 8, -1)])
+def test_wgrad_workspace_one_float_short_is_refused(lib, monkeypatch, ksize, up, C2, cfg):
+    """wmd_conv_wgrad checks the workspace against its plan before it launches anything: one float short -> WMD_ERR_WORKSPACE
+    (dummy non-null pointers never reach a kernel), on the Winograd, the direct 3x3 and the direct 1x1 path"""
+    monkeypatch.delenv("WMD_WGRAD_SMALLCO", raising=False)
+    cfg = lib.wmd_conv_wgrad_num_configs() if cfg == "last" else cfg
+    a = _lib.ConvWgradArgs(B=2, H=12, W=40, C1=24, up1=up, C2=C2, Cout=40, ksize=ksize, pad_mode=1, x1=1, x2=1 if C2 else None,
+                           dz=1, dw=1, dbias=1, workspace=None, workspace_floats=0, tune_cfg=cfg, tune_nsplit=0)
+    n = lib.wmd_conv_wgrad_workspace_floats(C.byref(a))
+    assert n > 0
+    a.workspace, a.workspace_floats = 1, n - 1
+    assert lib.wmd_conv_wgrad(C.byref(a), None) == -5
+    assert b"workspace" in lib.wmd_last_error()
+
+
+def test_wgrad_refusals_without_gpu(lib):
+    """wmd_conv_wgrad refuses before any HIP call: a 1x1 filter over an upsampled x1, a skip tensor without its pointer, and a
+    forced configuration that cannot run (past the Winograd table, below -1, a Winograd entry for a 1x1 filter) -- the last
+    is WMD_ERR_UNSUPPORTED with no workspace asked for, never the direct kernel in its place"""
+    n = lib.wmd_conv_wgrad_num_configs()
+    a = _lib.ConvWgradArgs(B=2, H=12, W=40, C1=24, up1=2, C2=0, Cout=40, ksize=1, pad_mode=0, x1=1, x2=None, dz=1, dw=1,
+                           dbias=1, workspace=None, workspace_floats=0, tune_cfg=0, tune_nsplit=0)
+    assert lib.wmd_conv_wgrad(C.byref(a), None) == -3                 # 1x1 with an upsampled x1
+    a.up1, a.C2 = 1, 8
+    assert lib.wmd_conv_wgrad(C.byref(a), None) == -1                 # C2 > 0, x2 NULL
+    assert b"x2" in lib.wmd_last_error()
+    a.x2 = 1
+    for ksize, cfg in ((3, n + 1), (3, n + 100), (3, -2), (1, -2), (1, 1), (1, n)):
+        a.ksize, a.tune_cfg = ksize, cfg
+        assert lib.wmd_conv_wgrad_workspace_floats(C.byref(a)) == 0, (ksize, cfg)
+        assert lib.wmd_conv_wgrad(C.byref(a), None) == -3, (ksize, cfg)
+        assert b"tune_cfg" in lib.wmd_last_error(), (ksize, cfg)
+    a.ksize, a.tune_cfg = 3, n                                          # the last entry is valid: only the workspace is missing
+    assert lib.wmd_conv_wgrad_workspace_floats(C.byref(a)) > 0
+    assert lib.wmd_conv_wgrad(C.byref(a), None) == -5
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from wavelet_monodepth_amd import ops

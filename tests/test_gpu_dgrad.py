@@ -7,10 +7,8 @@ weight images, zero padding, no activation), then conv_dgrad_fold_kernel folds t
 the (configuration, K split) pair by time alone, so every pair it may pick is compared here, forced through
 wmd_conv_dgrad_args.tune_cfg / tune_ksplit, every launch into NaN-filled outputs over a NaN-filled workspace.
 """
-import ast
 import collections
 import ctypes as C
-import json
 import os
 import zlib
 
@@ -19,7 +17,7 @@ import pytest
 import torch
 
 from oracle import decoder_ref as R
-from util import quarter_family_declines
+from util import bench_tune_cache_name, channel_subset, committed_entries, quarter_family_declines
 
 pytestmark = pytest.mark.gpu
 
@@ -383,34 +381,6 @@ def test_every_family_was_compared_in_dgrad_geometry():
 
 
 # ---- D. what bench.py runs: every committed choice at its own shape -------------------------------------------------------------
-def _bench_tune_cache_name():
-    """bench.TUNE_CACHE, read without executing bench.py (collection must not start anything); the test checks it against the
-    imported module"""
-    tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
-    for node in tree.body:
-        if isinstance(node, ast.Assign) and any(getattr(t_, "id", None) == "TUNE_CACHE" for t_ in node.targets):
-            return node.value.value
-    raise AssertionError("bench.py has no TUNE_CACHE")
-
-
-def _committed_entries():
-    with open(os.path.join(ROOT, "profiles", _bench_tune_cache_name())) as f:
-        return sorted((k, tuple(v)) for k, v in json.load(f).items())
-
-
-def channel_subset(n, tag):
-    """A deterministic subset of n channels: the first and last, both sides of the first two and the last 8 / 16 / 32-channel
-    boundaries, and six at random (fixed seed)."""
-    s = {0, n - 1}
-    for q in (8, 16, 32):
-        for b in (q, 2 * q, ((n - 1) // q) * q):
-            if 0 < b < n:
-                s.update((b - 1, b))
-    g = np.random.default_rng(zlib.crc32(tag.encode()))
-    s.update(int(v) for v in g.integers(0, n, 6))
-    return sorted(s)
-
-
 _BENCH = {}
 
 
@@ -429,14 +399,14 @@ def _err(got, ref):
 
 
 @pytest.mark.skipif(not WINOGRAD, reason="Winograd family switched off (WMD_WINOGRAD=0): the committed choices name it")
-@pytest.mark.parametrize("key,choice", _committed_entries(), ids=[k for k, _ in _committed_entries()])
+@pytest.mark.parametrize("key,choice", committed_entries(), ids=[k for k, _ in committed_entries()])
 def test_committed_tune_choice_vs_oracle(dev, key, choice):
     """Every conv| / dgrad| / wgrad| entry of the tile choices bench.py preloads, forced at the entry's own H, W and channels with
     B = 2, against the float64 oracle on a channel subset (forward y[co] needs only w[co]; dgrad dx[ci] only w[:, ci]; wgrad
     dW[co, ci] only dz[co] and x[ci]: the subset's values are exact, not approximated)."""
     from wavelet_monodepth_amd import _lib, ops, tuner
     bench = _bench_module()
-    assert bench.TUNE_CACHE == _bench_tune_cache_name()
+    assert bench.TUNE_CACHE == bench_tune_cache_name()
     kind, *f = key.split("|")
     _, H, W, C1, up, C2, Cout, k = (int(v) for v in f[:8])
     B, pad = 2, "reflect"

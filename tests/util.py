@@ -1,11 +1,15 @@
 """Shared helpers for the test-suite (golden loading, deterministic inputs, comparisons)."""
+import ast
+import json
 import os
+import zlib
 
 import numpy as np
 import torch
 
 from wavelet_monodepth_amd import synth
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 R18 = [64, 64, 128, 256, 512]
 R50 = [64, 256, 512, 1024, 2048]
@@ -147,3 +151,32 @@ def quarter_family_declines(name, C1, C2, masked=False, up=1, promise=1):
     if not name.startswith("conv_wino32q"):
         return False
     return (C1 + C2) % 8 != 0 or (C2 > 0 and C1 % 8 != 0) or (masked and up == 2 and not promise)
+
+
+def bench_tune_cache_name():
+    """bench.TUNE_CACHE, read without executing bench.py (collection must not start anything); the tests check it against the
+    imported module"""
+    tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
+    for node in tree.body:
+        if isinstance(node, ast.Assign) and any(getattr(t_, "id", None) == "TUNE_CACHE" for t_ in node.targets):
+            return node.value.value
+    raise AssertionError("bench.py has no TUNE_CACHE")
+
+
+def committed_entries():
+    """the tile choices bench.py preloads: sorted (key, (label, split)) pairs"""
+    with open(os.path.join(ROOT, "profiles", bench_tune_cache_name())) as f:
+        return sorted((k, tuple(v)) for k, v in json.load(f).items())
+
+
+def channel_subset(n, tag):
+    """A deterministic subset of n channels: the first and last, both sides of the first two and the last 8 / 16 / 32-channel
+    boundaries, and six at random (fixed seed)."""
+    s = {0, n - 1}
+    for q in (8, 16, 32):
+        for b in (q, 2 * q, ((n - 1) // q) * q):
+            if 0 < b < n:
+                s.update((b - 1, b))
+    g = np.random.default_rng(zlib.crc32(tag.encode()))
+    s.update(int(v) for v in g.integers(0, n, 6))
+    return sorted(s)

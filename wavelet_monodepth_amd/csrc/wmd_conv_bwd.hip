@@ -1016,8 +1016,14 @@ static SmallcoPlan smallco_plan(const wmd_conv_wgrad_args* g) {
 extern "C" int wmd_conv_wgrad_num_configs(void) { return kNumWWCfgs; }
 extern "C" const char* wmd_conv_wgrad_config_name(int index) { return (index >= 0 && index < kNumWWCfgs) ? kWWCfgs[index].name : ""; }
 
+// tune_cfg names a configuration that cannot run: an index past the Winograd table, below -1, or a Winograd entry for a
+// 1x1 filter.  Refused (WMD_ERR_UNSUPPORTED), never served by another kernel than the one asked for.
+static bool wgrad_forced_cfg_invalid(const wmd_conv_wgrad_args* g) {
+    return g->tune_cfg < -1 || g->tune_cfg > kNumWWCfgs || (g->tune_cfg > 0 && g->ksize != 3);
+}
+
 extern "C" size_t wmd_conv_wgrad_workspace_floats(const wmd_conv_wgrad_args* g) {
-    if (!g || g->B <= 0 || g->Cout <= 0) return 0;
+    if (!g || g->B <= 0 || g->Cout <= 0 || wgrad_forced_cfg_invalid(g)) return 0;
     if (smallco_wgrad(g)) return (size_t)smallco_plan(g).nsplit * ((size_t)g->Cout * g->C1 * 9 + g->Cout);
     WgradWinoPlan wp;
     if (plan_wgrad_wino(g, &wp)) return (size_t)wp.nsplit * (16 * (size_t)g->Cout * (g->C1 + g->C2) + g->Cout);
@@ -1034,6 +1040,9 @@ extern "C" int wmd_conv_wgrad(const wmd_conv_wgrad_args* g, void* stream) {
     int st = validate_bwd(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, "wmd_conv_wgrad");
     if (st) return st;
     if (g->ksize == 1 && g->up1 == 2) return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_wgrad: 1x1 with upsampled input");
+    if (wgrad_forced_cfg_invalid(g))
+        return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_wgrad: tune_cfg=%d cannot run (%d Winograd entries, 3x3 only; ksize=%d)", g->tune_cfg,
+                    kNumWWCfgs, g->ksize);
     if ((double)std::max(g->C1, std::max(g->C2, g->Cout)) * g->H * g->W * 4 > 2147483647.0)
         return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_wgrad: a per-image tensor slice exceeds 2 GiB");
     if (smallco_wgrad(g)) {
