@@ -26,7 +26,7 @@ for C, H, W in [(256, 12, 40), (128, 24, 80), (64, 48, 160), (32, 96, 320)]:
     fl = 2 * 2 * 27 * C * B * H * W
     print("head3x3 C=%3d %3dx%-3d: %7.1f us  %5.1f TFLOP/s" % (C, H, W, us, fl / us / 1e6))
 
-# full level (both heads + IDWT), one-launch vs two-launch form (WMD_TWO_LAUNCH_HEAD=1)
+# full level (both heads + IDWT): one launch at C = 32, wmd_head_fused_fwd + wmd_head_shiftsum_fwd at the wider levels
 for C, H, W in [(256, 12, 40), (128, 24, 80), (64, 48, 160), (32, 96, 320)]:
     x = torch.randn(B, C, H, W, device=dev)
     yl = torch.randn(B, 1, H, W, device=dev)

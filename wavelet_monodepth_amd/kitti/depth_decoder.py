@@ -64,10 +64,6 @@ class DepthWaveProgressiveDecoder(nn.Module):
         self.stack_heads = os.environ.get("WMD_STACKED_HEADS", "1") == "1"   # training: one launch per stage over all heads of a level
         self.branch_trace = None   # set to a dict to record the LeakyReLU pieces of a training-mode forward
         self.fuse_heads = True   # inference: fused 1x1 -> 3x3 -> IDWT head kernels where the width allows (32/64/128)
-        # opt-in: heads on a second stream -- 1: under graph capture only (a replayed graph serialises the fork: no gain), 2: eager
-        # launches too (side stream of priority WMD_OVERLAP_PRIO; tools/probes/overlap_probe.py)
-        self.overlap_heads = int(os.environ.get("WMD_OVERLAP_HEADS", "0"))
-        self._side_stream = None
         # graph mode: one graph (default), or trunk / heads as graph segments on two streams (WMD_TWO_STREAM_GRAPHS=1).  The
         # two-stream replay won 2-3 % while the trunk ran on the 16x16x4 Winograd kernels; beside conv_wino32_kernel (two
         # 200-register blocks per CU) the side-stream heads no longer find idle CUs: 0.648 vs 0.625 ms (round 3, same box)
@@ -79,6 +75,19 @@ class DepthWaveProgressiveDecoder(nn.Module):
         self._segments = {}
 
     # -- pieces ------------------------------------------------------------------------------
+    def _head_params(self, i, j):
+        """(w1, b1, w3, b3) of wavelet head (i, j): its Conv1x1 and its Conv3x3."""
+        m = self.convs[("waveconv", i, j)]
+        return m[0].conv.weight, m[0].conv.bias, m[2].conv.weight, m[2].conv.bias
+
+    def _store_level(self, i, yl, yh, disp):
+        """Level i's five outputs: its low-pass input yl, the three planes of yh [B,1,3,H,W] and its disparity."""
+        self.outputs[("wavelets", i - 1, "LL")] = yl
+        self.outputs[("wavelets", i - 1, "LH")] = yh[:, :, 0]
+        self.outputs[("wavelets", i - 1, "HL")] = yh[:, :, 1]
+        self.outputs[("wavelets", i - 1, "HH")] = yh[:, :, 2]
+        self.outputs[("disp", i - 1)] = disp
+
     def _head_mid(self, x, key, x_gate=None, gated=True):
         # the 1x1's LeakyReLU output `mid` is consumed by the head's 3x3 only, whose backward returns d mid * leaky'(mid)
         # (x_gate on that side): the 1x1's backward takes its incoming gradient as dz -- unless a hook could hand `mid` to
@@ -93,7 +102,7 @@ class DepthWaveProgressiveDecoder(nn.Module):
             return self._coefficients_stacked(input_features, scale, return_ll)
         stackable = all(self.convs[("waveconv", scale, j)][0].conv.weight.shape[0] % 16 == 0 for j in ([0] if return_ll else []) + [1])
         if self.stack_heads and stackable:   # (the stacked GEMM concatenates whole 16-channel tiles)
-            hd = lambda j: (lambda m: (m[0].conv.weight, m[0].conv.bias, m[2].conv.weight, m[2].conv.bias))(self.convs[("waveconv", scale, j)])
+            hd = lambda j: self._head_params(scale, j)
             yh, yl, mid = ops.stacked_heads(input_features, hd(1), hd(-1), 2.0 ** (scale - 1), hd(0) if return_ll else None,
                                             2.0 ** scale, x_gate=_x_gate, return_mid=True)
             if self.branch_trace is not None:   # which LeakyReLU piece each element took (gradient-parity diagnostics)
@@ -325,42 +334,15 @@ class DepthWaveProgressiveDecoder(nn.Module):
         ops.prepack_module(self)      # one launch for every weight image this pass (and its backward) will ask for
         x = input_features[-1]
         yl = None
-        # Under hipGraph capture the wavelet heads run on a second stream: head(i) needs only x_i and the low-pass of
-        # head(i+1), the trunk continues from x_i — two dependency chains.  The coarse-level heads are small launches
-        # (46 - 720 workgroups) and so are the coarse trunk convolutions: side by side they fill each other's idle CUs.
-        # (Capture only: there every buffer is static; the eager path stays on one stream.)  Measured on MI355X: 0.748 vs
-        # 0.743 ms per step -- the replayed graph gains nothing from the fork, so this stays opt-in (WMD_OVERLAP_HEADS=1).
-        overlap = bool(self.overlap_heads) and not torch.is_grad_enabled() and \
-            (torch.cuda.is_current_stream_capturing() or self.overlap_heads >= 2)
-        main = torch.cuda.current_stream() if overlap else None
-        if overlap and self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(priority=int(os.environ.get("WMD_OVERLAP_PRIO", "0")))
-        side = self._side_stream if overlap else None
-        keep = []   # tensors that cross streams stay referenced until the streams have joined
         # training: every consumer of a trunk activation (the next trunk convolution, the heads' 1x1 convolutions) returns its
         # data gradient already multiplied by ELU'(activation), so no trunk convolution runs a separate activation-backward
         # pass (ops.conv2d_fused: x1_gate / grad_is_dz)
         elu = ("elu", 0.0) if (torch.is_grad_enabled() and gated_backward_allowed(self)) else None
         self._gated = elu is not None
         edge = getattr(self, "_edge", None)
-        # dense inference: the heads of a level read only that level's trunk activation, so levels 4..2 are POSTPONED until
-        # upconv(2,1) is done: ONE launch runs their chained first stages (round 6, ops.head_fused_gemm_multi_nograd: alone none of
-        # these levels fills 256 CUs; config 2, batch 12: 0.082 -> 0.069 ms, one frame 0.202 -> 0.177 ms), ONE launch completes all
-        # three (round 5, ops.head_shiftsum_chain_nograd: level k's synthesis output is level k+1's low-pass input, pixel for pixel).
-        # Without the merged launch (WMD_HEAD_CHAIN_MULTI=0, odd plane sizes) every level launches its first stage in place and the
-        # chained completion is used up to WMD_SHIFTSUM_CHAIN_MAX_PIXELS only (it then reads planes that have left the caches).
-        widths = [int(self.num_ch_dec[k]) for k in (4, 3, 2)]
-        plain = (not overlap) and (not torch.is_grad_enabled()) and self.fuse_heads and \
-            bool(ops._lib.lib().wmd_head_level_supported(int(self.num_ch_dec[1])))
-        chain_multi = plain and edge is None and ops.head_chain_multi_supported(widths) and \
-            all((input_features[k].shape[2] * input_features[k].shape[3]) % 4 == 0 for k in (3, 2, 1))
-        chain = plain and ops.shiftsum_chain_supported(
-            widths, 0 if chain_multi else input_features[1].shape[0] * input_features[1].shape[2] * input_features[1].shape[3])
+        chain_multi, chain, pyramid = self._dense_route(input_features, edge)
+        scales, disp_scales = [2.0 ** (k - 1) for k in (4, 3, 2)], [1.0 / 2 ** (k - 1) for k in (4, 3, 2)]
         pending, deferred = [], []
-        # ... and (round 6) the completions of levels 4..2 run INSIDE level 1's launch: the streaming kernel's epilogue waves complete
-        # the coarser levels over each unit's footprint first (ops.head_level_pyramid_nograd): one graph node and 21.7 us fewer
-        f0 = input_features[0]
-        pyramid = chain and ops.head_level_pyramid_supported(int(self.num_ch_dec[1]), f0.shape[0], f0.shape[2], f0.shape[3])
         for i in range(4, 0, -1):
             if i == 4 and edge is not None:
                 x = self.convs[("upconv", 4, 0)](x, x1_pre=edge.pre())      # ReLU (+ affine) of the encoder's last block on load
@@ -368,58 +350,48 @@ class DepthWaveProgressiveDecoder(nn.Module):
                 x = self.convs[("upconv", i, 0)](x, x1_gate=elu if i < 4 else None, grad_is_dz=elu is not None)
             skip = input_features[i - 1] if (self.use_skips and i > 0) else None
             x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, x1_gate=elu, grad_is_dz=elu is not None)  # fused upsample + concat
-            if chain and i >= 2:
-                hd = lambda j: (lambda m: (m[0].conv.weight, m[0].conv.bias, m[2].conv.weight, m[2].conv.bias))(self.convs[("waveconv", i, j)])
+            if chain and i >= 2:        # levels 4..2: first stage now or deferred, then one completion launch (see _dense_route)
+                level = (x, self._head_params(i, 1), self._head_params(i, -1), self._head_params(i, 0) if i == 4 else None)
                 if chain_multi:
-                    deferred.append((x, hd(1), hd(-1), hd(0) if i == 4 else None))
+                    deferred.append(level)
                     if i == 2:
                         pending = ops.head_fused_gemm_multi_nograd(deferred)
                 else:
-                    pending.append(ops.head_fused_gemm_nograd(x, hd(1), hd(-1), hd(0) if i == 4 else None))
-                if i == 2 and pyramid:
-                    continue        # ... completed inside level 1's launch (below)
-                if i == 2:
-                    done = ops.head_shiftsum_chain_nograd(pending, [2.0 ** (k - 1) for k in (4, 3, 2)], [1.0 / 2 ** (k - 1) for k in (4, 3, 2)],
-                                                          scale_ll=2.0 ** 4)
-                    for k, (yh, out, disp, yl_ll) in zip((4, 3, 2), done):
-                        self.outputs[("wavelets", k - 1, "LL")] = yl_ll if k == 4 else yl
-                        self.outputs[("wavelets", k - 1, "LH")] = yh[:, :, 0]
-                        self.outputs[("wavelets", k - 1, "HL")] = yh[:, :, 1]
-                        self.outputs[("wavelets", k - 1, "HH")] = yh[:, :, 2]
-                        self.outputs[("disp", k - 1)] = disp
-                        yl = out
-                continue
-            if pyramid and i == 1:
-                hp, hn = self.convs[("waveconv", 1, 1)], self.convs[("waveconv", 1, -1)]
-                hw = lambda m: (m[0].conv.weight, m[0].conv.bias, m[2].conv.weight, m[2].conv.bias)
-                done, (yh, out, disp) = ops.head_level_pyramid_nograd(
-                    x, hw(hp), hw(hn), 1.0, 1.0, pending, [2.0 ** (k - 1) for k in (4, 3, 2)], [1.0 / 2 ** (k - 1) for k in (4, 3, 2)],
-                    scale_ll=2.0 ** 4)
-                for k, (yhk, outk, dispk, yl_ll) in zip((4, 3, 2), done):
-                    self.outputs[("wavelets", k - 1, "LL")] = yl_ll if k == 4 else yl
-                    self.outputs[("wavelets", k - 1, "LH")] = yhk[:, :, 0]
-                    self.outputs[("wavelets", k - 1, "HL")] = yhk[:, :, 1]
-                    self.outputs[("wavelets", k - 1, "HH")] = yhk[:, :, 2]
-                    self.outputs[("disp", k - 1)] = dispk
-                    yl = outk
-                self.outputs[("wavelets", 0, "LL")] = yl
-                self.outputs[("wavelets", 0, "LH")] = yh[:, :, 0]
-                self.outputs[("wavelets", 0, "HL")] = yh[:, :, 1]
-                self.outputs[("wavelets", 0, "HH")] = yh[:, :, 2]
-                self.outputs[("disp", 0)] = disp
-                yl = out
-                continue
-            if overlap:
-                keep.append(x)
-                x.record_stream(side)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    yl = self._level_heads(i, x, yl)
+                    pending.append(ops.head_fused_gemm_nograd(*level))
+                if i == 2 and not pyramid:
+                    yl = self._store_completed(ops.head_shiftsum_chain_nograd(pending, scales, disp_scales, scale_ll=2.0 ** 4), yl)
+            elif pyramid and i == 1:    # ... whose completions run inside level 1's launch
+                done, (yh, out, disp) = ops.head_level_pyramid_nograd(x, self._head_params(1, 1), self._head_params(1, -1), 1.0, 1.0,
+                                                                      pending, scales, disp_scales, scale_ll=2.0 ** 4)
+                yl = self._store_completed(done + [(yh, out, disp, None)], yl)
             else:
                 yl = self._level_heads(i, x, yl)
-        if overlap:
-            main.wait_stream(side)
         return self.outputs
+
+    def _dense_route(self, input_features, edge):
+        """Dense inference: how levels 4..2 run their heads -> (chain_multi, chain, pyramid), all False otherwise.  A level's heads
+        read only its trunk activation, so with `chain` each of levels 4..2 launches its first stage as the trunk reaches it, or
+        (`chain_multi`) all three run as ONE launch after upconv(2,1): alone none of them fills 256 CUs (config 2: 0.082 -> 0.069 ms).
+        ONE launch then completes all three, level k's synthesis output being level k+1's low-pass input -- without the merged first
+        stage only up to WMD_SHIFTSUM_CHAIN_MAX_PIXELS, as the planes have left the caches by then.  With `pyramid` that completion
+        runs inside level 1's launch (ops.head_level_pyramid_nograd: one graph node and 21.7 us fewer)."""
+        if torch.is_grad_enabled() or not self.fuse_heads or not ops._lib.lib().wmd_head_level_supported(int(self.num_ch_dec[1])):
+            return False, False, False
+        widths = [int(self.num_ch_dec[k]) for k in (4, 3, 2)]
+        f = input_features
+        chain_multi = edge is None and ops.head_chain_multi_supported(widths) and \
+            all((f[k].shape[2] * f[k].shape[3]) % 4 == 0 for k in (3, 2, 1))
+        chain = ops.shiftsum_chain_supported(widths, 0 if chain_multi else f[1].shape[0] * f[1].shape[2] * f[1].shape[3])
+        pyramid = chain and ops.head_level_pyramid_supported(int(self.num_ch_dec[1]), f[0].shape[0], f[0].shape[2], f[0].shape[3])
+        return chain_multi, chain, pyramid
+
+    def _store_completed(self, done, yl):
+        """Stores the levels 4, 3, ... that one launch completed (done: (yh, out, disp, yl_ll or None) per level, coarse to fine;
+        yl: the low-pass input of the first, unless it carries its own) -> the last one's synthesis output."""
+        for i, (yh, out, disp, yl_ll) in zip((4, 3, 2, 1), done):
+            self._store_level(i, yl_ll if yl_ll is not None else yl, yh, disp)
+            yl = out
+        return yl
 
     def _fused_train_ok(self, i, x):
         """Training mode: may level i's heads + synthesis run as ops.fused_level_train?  (Same conditions as the stacked form
@@ -432,58 +404,37 @@ class DepthWaveProgressiveDecoder(nn.Module):
 
     def _level_heads(self, i, x, yl):
         """Coefficients, IDWT and disparity of level i from the trunk activation x (and the previous low-pass yl)."""
-        fused = (not torch.is_grad_enabled()) and int(self.num_ch_dec[i]) in ops.FUSED_HEAD_WIDTHS and self.fuse_heads
-        if fused:
+        # the LL head (C -> C/4 -> 1) exists only at the coarsest level: a third chain of the same launches
+        hp, hn, hl = self._head_params(i, 1), self._head_params(i, -1), self._head_params(i, 0) if i == 4 else None
+        if (not torch.is_grad_enabled()) and int(self.num_ch_dec[i]) in ops.FUSED_HEAD_WIDTHS and self.fuse_heads:
             # one launch (C = 32) or two (1x1 -> LeakyReLU -> tap-partials with mid on chip, then 9-tap gather + sigmoid +
             # combine + Haar synthesis)
-            hp, hn = self.convs[("waveconv", i, 1)], self.convs[("waveconv", i, -1)]
-            head_ll = None
-            if i == 4:   # the LL head (C -> C/4 -> 1) exists only at the coarsest level: a third chain of the same launches
-                h0 = self.convs[("waveconv", i, 0)]
-                head_ll = (h0[0].conv.weight, h0[0].conv.bias, h0[2].conv.weight, h0[2].conv.bias)
-            yl_in = yl
-            res = ops.head_fused_level_nograd(
-                x, (hp[0].conv.weight, hp[0].conv.bias, hp[2].conv.weight, hp[2].conv.bias),
-                (hn[0].conv.weight, hn[0].conv.bias, hn[2].conv.weight, hn[2].conv.bias),
-                scale=2.0 ** (i - 1), yl=yl, disp_scale=1.0 / 2 ** (i - 1), clamp01=True, head_ll=head_ll, scale_ll=2.0 ** i)
-            yh, yl, disp = res[:3]
-            if head_ll is not None:
-                yl_in = res[3]
-            self.outputs[("wavelets", i - 1, "LL")] = yl_in
+            res = ops.head_fused_level_nograd(x, hp, hn, scale=2.0 ** (i - 1), yl=yl, disp_scale=1.0 / 2 ** (i - 1), clamp01=True,
+                                              head_ll=hl, scale_ll=2.0 ** i)
+            yh, out, disp = res[:3]
+            yl_in = res[3] if i == 4 else yl
         elif self._fused_train_ok(i, x):
             # training forward on the same fused kernels (round 5, ops._FusedLevelFn): heads + synthesis of the level as ONE
             # autograd node that keeps the 1x1 outputs and the sigmoid outputs for the hand-written backward
             gate = ("elu", 0.0) if getattr(self, "_gated", False) else None
-            hd = lambda j: (lambda m: (m[0].conv.weight, m[0].conv.bias, m[2].conv.weight, m[2].conv.bias))(self.convs[("waveconv", i, j)])
-            yl_in = yl
-            yh, yl_ll, yl, disp, mid = ops.fused_level_train(x, hd(1), hd(-1), 2.0 ** (i - 1), yl=None if i == 4 else yl,
-                                                             disp_scale=1.0 / 2 ** (i - 1), clamp01=True,
-                                                             head_ll=hd(0) if i == 4 else None, scale_ll=2.0 ** i, x_gate=gate)
-            if i == 4:
-                yl_in = yl_ll
+            yh, yl_ll, out, disp, mid = ops.fused_level_train(x, hp, hn, 2.0 ** (i - 1), yl=None if i == 4 else yl,
+                                                              disp_scale=1.0 / 2 ** (i - 1), clamp01=True, head_ll=hl,
+                                                              scale_ll=2.0 ** i, x_gate=gate)
+            yl_in = yl_ll if i == 4 else yl
             if self.branch_trace is not None:   # which LeakyReLU piece each element took (gradient-parity diagnostics)
                 o = 0
                 for j in ([0] if i == 4 else []) + [1, -1]:
                     c = self.convs[("waveconv", i, j)][0].conv.weight.shape[0]
                     self.branch_trace[("waveconv", i, j)] = (mid[:, o:o + c] > 0).cpu()
                     o += c
-            self.outputs[("wavelets", i - 1, "LL")] = yl_in
             yh = yh.unsqueeze(1)
-            fused = True
         else:
             gate = ("elu", 0.0) if (torch.is_grad_enabled() and getattr(self, "_gated", False)) else None   # x is this decoder's own ELU output, its producer expects dz (see _forward_impl)
-            if i == 4:
-                yl, yh = self.get_coefficients(x, scale=i, return_ll=True, _x_gate=gate)
-            else:
-                _, yh = self.get_coefficients(x, scale=i, return_ll=False, _x_gate=gate)
-            self.outputs[("wavelets", i - 1, "LL")] = yl
-        self.outputs[("wavelets", i - 1, "LH")] = yh[:, :, 0]
-        self.outputs[("wavelets", i - 1, "HL")] = yh[:, :, 1]
-        self.outputs[("wavelets", i - 1, "HH")] = yh[:, :, 2]
-        if not fused:
-            yl, disp = ops.idwt_haar(yl, yh, disp_scale=1.0 / 2 ** (i - 1), clamp01=True)
-        self.outputs[("disp", i - 1)] = disp
-        return yl
+            ll, yh = self.get_coefficients(x, scale=i, return_ll=i == 4, _x_gate=gate)
+            yl_in = ll if i == 4 else yl
+            out, disp = ops.idwt_haar(yl_in, yh, disp_scale=1.0 / 2 ** (i - 1), clamp01=True)
+        self._store_level(i, yl_in, yh, disp)
+        return out
 
 
 class DepthDecoder(nn.Module):

@@ -850,15 +850,76 @@ _HEAD_BWD_MERGED = os.environ.get("WMD_HEAD_BWD_MERGED", "1") != "0"   # 0: wmd_
 _HEAD_BWD_MIN_PIXELS = int(os.environ.get("WMD_HEAD_BWD_MIN_PIXELS", "16384"))
 _HEAD_BWD1_MIN_PIXELS = int(os.environ.get("WMD_HEAD_BWD1_MIN_PIXELS", "196608"))     # same for the 1x1 stage (wmd_head1x1_bwd):
 # its kernels walk the whole channel sum per 64-pixel wave tile and only win where a level has thousands of tiles (the finest one)
-_TWO_LAUNCH_HEAD = os.environ.get("WMD_TWO_LAUNCH_HEAD", "0") == "1"   # development switch: A/B the two forms
-_LL_FOLD = os.environ.get("WMD_LL_FOLD", "1") != "0"                   # 0: the low-pass head on its own three launches
-_LL_MERGE = os.environ.get("WMD_LL_MERGE", "1") != "0"                 # 0: the low-pass chain as a launch of its own (round 3)
 
 
 def head_level_folds_range_keys(C_):
     """True when head_fused_level_nograd(range_keys=...) at this width runs the two-launch form, whose second launch maintains
     the keys (the one-launch kernel of the finest level has no level after it that could want them)."""
-    return not (bool(_lib.lib().wmd_head_level_supported(int(C_))) and not _TWO_LAUNCH_HEAD)
+    return not _lib.lib().wmd_head_level_supported(int(C_))
+
+
+def _head_fused_args(x, head_p, head_n, head_ll=None, **extra):
+    """Arguments of wmd_head_fused_fwd (1x1 -> LeakyReLU -> 54 tap-partial planes; head_ll: the coarsest level's low-pass chain
+    rides along in planes 54..62 of 81) -> (HeadFusedArgs, item).  extra: further HeadFusedArgs fields.  item: what the
+    completion needs (t, B, H, W, b3p, b3n, b3l, has_ll) and `keep`, the contiguous copies and weight images the launch reads."""
+    x = _c(x)
+    B, Cc, H, W = x.shape
+    (w1p, b1p, w3p, b3p), (w1n, b1n, w3n, b3n) = head_p, head_n
+    wp1, bias1 = stacked_pack([w1p, w1n], [b1p, b1n])
+    wp2 = _tap_partial_pack(w3p, w3n)
+    planes = 81 if head_ll is not None else 54
+    t = torch.empty((B, planes, H, W), device=x.device, dtype=torch.float32)
+    a = _lib.HeadFusedArgs(B=B, H=H, W=W, C=Cc, slope=0.1, x=ptr(x), wp1=ptr(wp1), bias1=ptr(bias1), wp2=ptr(wp2), t=ptr(t),
+                           chain=0, t_planes=planes, **extra)
+    keep = [x, wp1, bias1, wp2]
+    b3l = None
+    if head_ll is not None:
+        w1l, b1l, w3l, b3l = head_ll
+        wpl1, wpl2 = _ll_chain_pack(w1l, w3l)
+        b1l_c = _c(b1l.detach())
+        a.ll_wp1, a.ll_bias1, a.ll_wp2 = ptr(wpl1), ptr(b1l_c), ptr(wpl2)
+        keep += [wpl1, wpl2, b1l_c]
+    return a, dict(t=t, B=B, H=H, W=W, b3p=b3p, b3n=b3n, b3l=b3l, has_ll=head_ll is not None, keep=keep)
+
+
+def _head_level_args(x, head_p, head_n, scale, yh, out, disp, disp_scale, clamp01, **extra):
+    """Arguments of wmd_head_level_fwd / wmd_head_level_pyramid_fwd (x contiguous) -> (HeadLevelArgs, the weight images the
+    launch reads).  extra: further HeadLevelArgs fields."""
+    B, Cc, H, W = x.shape
+    (w1p, b1p, w3p, b3p), (w1n, b1n, w3n, b3n) = head_p, head_n
+    wp1, bias1 = stacked_pack([w1p, w1n], [b1p, b1n])
+    wp2 = _tap_partial_pack(w3p, w3n)
+    a = _lib.HeadLevelArgs(B=B, H=H, W=W, C=Cc, pad_mode=PAD["reflect"], slope=0.1, scale=float(scale), x=ptr(x), wp1=ptr(wp1),
+                           bias1=ptr(bias1), wp2=ptr(wp2), bias_p=ptr(b3p), bias_n=ptr(b3n), yh=ptr(yh), out=ptr(out),
+                           disp=ptr(disp), disp_scale=float(disp_scale or 1.0), clamp01=int(clamp01), **extra)
+    return a, (wp1, bias1, wp2)
+
+
+def _shiftsum_args(items, scales, disp_scales, yl, scale_ll, clamp01):
+    """Arguments that complete consecutive levels (items of head_fused_gemm[_multi]_nograd, coarse to fine) -> (HeadShiftsumArgs
+    array, (yh [B,1,3,H,W], out [B,1,2H,2W], disp, yl_ll or None) per level, the contiguous yl).  The first level takes its
+    low-pass input from yl or from the low-pass head its item carries, every later one from the level before."""
+    has_ll = items[0]["has_ll"]
+    if not has_ll and yl is None:
+        raise _lib.WmdError("head completion: the first level needs its low-pass input (yl) or the low-pass head")
+    # held until after the launch: a dropped temporary's block could be handed to yh / out / disp below
+    yl_c = _c(yl) if (yl is not None and not has_ll) else None
+    arr = (_lib.HeadShiftsumArgs * len(items))()
+    res = []
+    for k, it in enumerate(items):
+        B, H, W = it["B"], it["H"], it["W"]
+        dev = it["t"].device
+        yh = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+        out = torch.empty((B, 1, 2 * H, 2 * W), device=dev, dtype=torch.float32)
+        disp = torch.empty_like(out)
+        yl_ll = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if (k == 0 and has_ll) else None
+        arr[k] = _lib.HeadShiftsumArgs(B=B, H=H, W=W, pad_mode=PAD["reflect"], scale=float(scales[k]), t=ptr(it["t"]),
+                                       bias_p=ptr(it["b3p"]), bias_n=ptr(it["b3n"]), yh=ptr(yh), yl=ptr(yl_c) if k == 0 else None,
+                                       out=ptr(out), disp=ptr(disp), disp_scale=float(disp_scales[k]), clamp01=int(clamp01),
+                                       bias_ll=ptr(it["b3l"]) if yl_ll is not None else None, scale_ll=float(scale_ll),
+                                       yl_out=ptr(yl_ll))
+        res.append((yh.unsqueeze(1), out, disp, yl_ll))
+    return arr, res, yl_c
 
 
 def head_fused_level_nograd(x, head_p, head_n, scale, yl=None, disp_scale=None, clamp01=False, head_ll=None, scale_ll=1.0,
@@ -867,8 +928,8 @@ def head_fused_level_nograd(x, head_p, head_n, scale, yl=None, disp_scale=None, 
     wmd_head_level_fwd, every intermediate in LDS) or two: wmd_head_fused_fwd (1x1 -> LeakyReLU -> 27 tap-partials per
     side, intermediate stays on chip) and wmd_head_shiftsum_fwd (9-tap gather, bias, sigmoid, combine, IDWT).
     head_* = (w1, b1, w3, b3).  head_ll: the coarsest level's low-pass head (C -> C/4 -> 1, sigmoid * scale_ll); at C = 256
-    it is a small third launch of the same fused kernel (tap-partials into planes 54..62 of the shared buffer) that the
-    shift-sum completes and feeds to the synthesis as its low-pass input (yl must be None); other widths: own operators.
+    it rides in the first launch (tap-partials into planes 54..62 of the shared buffer), and the shift-sum completes it and
+    feeds it to the synthesis as its low-pass input (yl must be None); other widths: own operators.
     yh_mask (uint8 [B,H,W]): yh is zeroed outside it before the store and the synthesis (depth_decoder.py:272).
     run_mask (uint8 [B,H,W], two-launch form): pixel runs without a set byte skip the GEMMs (wmd_head_fused_args.run_mask);
     range_keys (int32 [B,2], two-launch form): the (min, max) of the new low-pass plane are folded into it by the second
@@ -885,19 +946,16 @@ def head_fused_level_nograd(x, head_p, head_n, scale, yl=None, disp_scale=None, 
         raise _lib.WmdError("head_fused_level_nograd: no fused training forward for C=%d, %dx%d%s" % (Cc, H, W, " + LL" if head_ll is not None else ""))
     if yh_mask is not None and (yh_mask.dtype != torch.uint8 or yh_mask.numel() != B * H * W or not yh_mask.is_contiguous()):
         raise _lib.WmdError("head_fused_level_nograd: yh_mask must be a contiguous uint8 [B,H,W] tensor")
-    (w1p, b1p, w3p, b3p), (w1n, b1n, w3n, b3n) = head_p, head_n
-    one_launch = bool(l.wmd_head_level_supported(Cc)) and not _TWO_LAUNCH_HEAD
+    one_launch = bool(l.wmd_head_level_supported(Cc))
     yl_ll = None
     if head_ll is not None:
         if yl is not None:
             raise _lib.WmdError("head_fused_level_nograd: head_ll supplies the low-pass input; yl must be None")
-        w1l, b1l, w3l, b3l = head_ll
-        if one_launch or Cc != 256 or not _LL_FOLD:     # the low-pass head on its own operators
+        if one_launch or Cc != 256:     # the low-pass head on its own operators
+            w1l, b1l, w3l, b3l = head_ll
             mid0 = conv2d_fused(x, w1l, b1l, pad="zero", act="leaky", slope=0.1)
             yl = yl_ll = head3x3(mid0, w3l, b3l, pad="reflect", mode=1, scale=scale_ll)
             head_ll = None
-    wp1, bias1 = stacked_pack([w1p, w1n], [b1p, b1n])
-    wp2 = _tap_partial_pack(w3p, w3n)
     s = current_stream()
     yh = torch.empty((B, 3, H, W), device=x.device, dtype=torch.float32)
     out = disp = None
@@ -907,38 +965,22 @@ def head_fused_level_nograd(x, head_p, head_n, scale, yl=None, disp_scale=None, 
         disp = torch.empty_like(out) if disp_scale is not None else None
     if one_launch:
         # one launch: every intermediate of the level stays in LDS
-        a = _lib.HeadLevelArgs(B=B, H=H, W=W, C=Cc, pad_mode=PAD["reflect"], slope=0.1, scale=float(scale), x=ptr(x),
-                               wp1=ptr(wp1), bias1=ptr(bias1), wp2=ptr(wp2), bias_p=ptr(b3p), bias_n=ptr(b3n), yh=ptr(yh),
-                               yl=ptr(yl), out=ptr(out), disp=ptr(disp), disp_scale=float(disp_scale or 1.0),
-                               clamp01=int(clamp01), yh_mask=ptr(yh_mask))
+        a, _keep = _head_level_args(x, head_p, head_n, scale, yh, out, disp, disp_scale, clamp01, yl=ptr(yl), yh_mask=ptr(yh_mask))
         if train is not None:
             a.mid_out, a.mid_ct, a.mid_off_p, a.mid_off_n = ptr(tr["mid"]), tr["mid"].shape[1], tr["off_p"], tr["off_n"]
             a.sig_p, a.sig_n = ptr(tr["sig_p"]), ptr(tr["sig_n"])
         check(l.wmd_head_level_fwd(C.byref(a), s), "wmd_head_level_fwd")
     else:
-        planes = 81 if head_ll is not None else 54
-        t = torch.empty((B, planes, H, W), device=x.device, dtype=torch.float32)
-        a = _lib.HeadFusedArgs(B=B, H=H, W=W, C=Cc, slope=0.1, x=ptr(x), wp1=ptr(wp1), bias1=ptr(bias1), wp2=ptr(wp2), t=ptr(t),
-                               chain=0, t_planes=planes, run_mask=ptr(run_mask))
-        if head_ll is not None:     # the low-pass chain rides in the same call (planes 54..62): a third group of workgroups of
-            wpl1, wpl2 = _ll_chain_pack(w1l, w3l)       # the chained kernel's launch, or a second launch issued by the library
+        mids = {} if train is None else dict(mid_out=ptr(tr["mid"]), mid_ct=tr["mid"].shape[1], mid_off_p=tr["off_p"],
+                                             mid_off_n=tr["off_n"], mid_off_ll=tr.get("off_ll", 0))
+        a, it = _head_fused_args(x, head_p, head_n, head_ll, run_mask=ptr(run_mask), **mids)
+        if head_ll is not None:
             yl_ll = torch.empty((B, 1, H, W), device=x.device, dtype=torch.float32)
-            b1l_c = _c(b1l.detach())
-            if _LL_MERGE:
-                a.ll_wp1, a.ll_bias1, a.ll_wp2 = ptr(wpl1), ptr(b1l_c), ptr(wpl2)
-        if train is not None:
-            a.mid_out, a.mid_ct, a.mid_off_p, a.mid_off_n = ptr(tr["mid"]), tr["mid"].shape[1], tr["off_p"], tr["off_n"]
-            a.mid_off_ll = tr.get("off_ll", 0)
         check(l.wmd_head_fused_fwd(C.byref(a), s), "wmd_head_fused_fwd")
-        if head_ll is not None and not _LL_MERGE:
-            a = _lib.HeadFusedArgs(B=B, H=H, W=W, C=Cc, slope=0.1, x=ptr(x), wp1=ptr(wpl1), bias1=ptr(b1l_c), wp2=ptr(wpl2),
-                                   t=ptr(t), chain=1, t_planes=planes)
-            check(l.wmd_head_fused_fwd(C.byref(a), s), "wmd_head_fused_fwd")
-        g = _lib.HeadShiftsumArgs(B=B, H=H, W=W, pad_mode=PAD["reflect"], scale=float(scale), t=ptr(t), bias_p=ptr(b3p),
-                                  bias_n=ptr(b3n), yh=ptr(yh), yl=ptr(yl), out=ptr(out), disp=ptr(disp),
-                                  disp_scale=float(disp_scale or 1.0), clamp01=int(clamp01),
-                                  bias_ll=ptr(b3l) if head_ll is not None else None, scale_ll=float(scale_ll),
-                                  yl_out=ptr(yl_ll) if head_ll is not None else None, yh_mask=ptr(yh_mask),
+        g = _lib.HeadShiftsumArgs(B=B, H=H, W=W, pad_mode=PAD["reflect"], scale=float(scale), t=ptr(it["t"]), bias_p=ptr(it["b3p"]),
+                                  bias_n=ptr(it["b3n"]), yh=ptr(yh), yl=ptr(yl), out=ptr(out), disp=ptr(disp),
+                                  disp_scale=float(disp_scale or 1.0), clamp01=int(clamp01), bias_ll=ptr(it["b3l"]),
+                                  scale_ll=float(scale_ll), yl_out=ptr(yl_ll) if head_ll is not None else None, yh_mask=ptr(yh_mask),
                                   range_keys=ptr(range_keys) if out is not None else None)
         if train is not None:
             g.sig_p, g.sig_n = ptr(tr["sig_p"]), ptr(tr["sig_n"])
@@ -962,7 +1004,7 @@ def shiftsum_chain_supported(widths, finest_pixels=0):
     completes itself) and the coarsest low-pass head must ride in the C = 256 launch; finest_pixels = B*H*W of the last level
     (the launch pays for latency-bound forwards only: _SHIFTSUM_CHAIN_MAX_PIXELS)."""
     l = _lib.lib()
-    return (_SHIFTSUM_CHAIN and finest_pixels <= _SHIFTSUM_CHAIN_MAX_PIXELS and not _TWO_LAUNCH_HEAD and 1 <= len(widths) <= 3 and _LL_FOLD and _LL_MERGE and _HEAD_CHAIN_ON and
+    return (_SHIFTSUM_CHAIN and finest_pixels <= _SHIFTSUM_CHAIN_MAX_PIXELS and 1 <= len(widths) <= 3 and _HEAD_CHAIN_ON and
             all(int(c) in (64, 128, 256) and not l.wmd_head_level_supported(int(c)) for c in widths) and int(widths[0]) == 256)
 
 
@@ -975,24 +1017,8 @@ def head_fused_gemm_multi_nograd(levels):
     arr = (_lib.HeadFusedArgs * n)()
     items = []
     for k, (x, head_p, head_n, head_ll) in enumerate(levels):
-        x = _c(x)
-        B, Cc, H, W = x.shape
-        (w1p, b1p, w3p, b3p), (w1n, b1n, w3n, b3n) = head_p, head_n
-        wp1, bias1 = stacked_pack([w1p, w1n], [b1p, b1n])
-        wp2 = _tap_partial_pack(w3p, w3n)
-        planes = 81 if head_ll is not None else 54
-        t = torch.empty((B, planes, H, W), device=x.device, dtype=torch.float32)
-        arr[k] = _lib.HeadFusedArgs(B=B, H=H, W=W, C=Cc, slope=0.1, x=ptr(x), wp1=ptr(wp1), bias1=ptr(bias1), wp2=ptr(wp2), t=ptr(t),
-                                    chain=0, t_planes=planes)
-        keep = [x, wp1, bias1, wp2]
-        b3l = None
-        if head_ll is not None:
-            w1l, b1l, w3l, b3l = head_ll
-            wpl1, wpl2 = _ll_chain_pack(w1l, w3l)
-            b1l_c = _c(b1l.detach())
-            arr[k].ll_wp1, arr[k].ll_bias1, arr[k].ll_wp2 = ptr(wpl1), ptr(b1l_c), ptr(wpl2)
-            keep += [wpl1, wpl2, b1l_c]
-        items.append(dict(t=t, B=B, H=H, W=W, b3p=b3p, b3n=b3n, b3l=b3l, has_ll=head_ll is not None, keep=keep))
+        arr[k], it = _head_fused_args(x, head_p, head_n, head_ll)
+        items.append(it)
     check(l.wmd_head_fused_multi_fwd(arr, n, current_stream()), "wmd_head_fused_multi_fwd")
     return items
 
@@ -1000,22 +1026,9 @@ def head_fused_gemm_multi_nograd(levels):
 def head_shiftsum_item_nograd(item, scale, disp_scale, yl=None, scale_ll=1.0, clamp01=True):
     """Completes ONE level from an item of head_fused_gemm[_multi]_nograd (wmd_head_shiftsum_fwd): -> (yh [B,1,3,H,W], out, disp,
     yl_ll or None).  yl: the level's low-pass input (None for the level whose item carries the low-pass head)."""
-    l = _lib.lib()
-    B, H, W = item["B"], item["H"], item["W"]
-    dev = item["t"].device
-    yh = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
-    out = torch.empty((B, 1, 2 * H, 2 * W), device=dev, dtype=torch.float32)
-    disp = torch.empty_like(out)
-    yl_ll = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if item["has_ll"] else None
-    if yl_ll is None and yl is None:
-        raise _lib.WmdError("head_shiftsum_item_nograd: the level needs its low-pass input (yl) or the low-pass head")
-    yl_c = _c(yl) if (yl is not None and yl_ll is None) else None
-    g = _lib.HeadShiftsumArgs(B=B, H=H, W=W, pad_mode=PAD["reflect"], scale=float(scale), t=ptr(item["t"]), bias_p=ptr(item["b3p"]),
-                              bias_n=ptr(item["b3n"]), yh=ptr(yh), yl=ptr(yl_c), out=ptr(out), disp=ptr(disp), disp_scale=float(disp_scale),
-                              clamp01=int(clamp01), bias_ll=ptr(item["b3l"]) if yl_ll is not None else None, scale_ll=float(scale_ll),
-                              yl_out=ptr(yl_ll))
-    check(l.wmd_head_shiftsum_fwd(C.byref(g), current_stream()), "wmd_head_shiftsum_fwd")
-    return yh.unsqueeze(1), out, disp, yl_ll
+    arr, res, _yl_c = _shiftsum_args([item], [scale], [disp_scale], yl, scale_ll, clamp01)
+    check(_lib.lib().wmd_head_shiftsum_fwd(arr, current_stream()), "wmd_head_shiftsum_fwd")
+    return res[0]
 
 
 _HEAD_CHAIN_MULTI = os.environ.get("WMD_HEAD_CHAIN_MULTI", "1") != "0"   # 0: every level's first stage as a launch of its own
@@ -1024,61 +1037,24 @@ _HEAD_CHAIN_MULTI = os.environ.get("WMD_HEAD_CHAIN_MULTI", "1") != "0"   # 0: ev
 def head_chain_multi_supported(widths):
     """Dense inference: may the first stages of these levels (coarse to fine) be postponed and run as ONE launch?"""
     l = _lib.lib()
-    return (_HEAD_CHAIN_MULTI and not _TWO_LAUNCH_HEAD and 2 <= len(widths) <= 3 and _LL_FOLD and _LL_MERGE and _HEAD_CHAIN_ON and
+    return (_HEAD_CHAIN_MULTI and 2 <= len(widths) <= 3 and _HEAD_CHAIN_ON and
             all(int(c) in (64, 128, 256) and not l.wmd_head_level_supported(int(c)) for c in widths))
 
 
 def head_fused_gemm_nograd(x, head_p, head_n, head_ll=None):
     """First launch of the two-launch head form alone (wmd_head_fused_fwd: 1x1 -> LeakyReLU -> tap-partial planes, the coarsest
     level's low-pass chain riding along): -> what head_shiftsum_chain_nograd needs to complete the level later."""
-    l = _lib.lib()
-    x = _c(x)
-    B, Cc, H, W = x.shape
-    (w1p, b1p, w3p, b3p), (w1n, b1n, w3n, b3n) = head_p, head_n
-    wp1, bias1 = stacked_pack([w1p, w1n], [b1p, b1n])
-    wp2 = _tap_partial_pack(w3p, w3n)
-    planes = 81 if head_ll is not None else 54
-    t = torch.empty((B, planes, H, W), device=x.device, dtype=torch.float32)
-    a = _lib.HeadFusedArgs(B=B, H=H, W=W, C=Cc, slope=0.1, x=ptr(x), wp1=ptr(wp1), bias1=ptr(bias1), wp2=ptr(wp2), t=ptr(t),
-                           chain=0, t_planes=planes)
-    keep = [x, wp1, bias1, wp2]
-    b3l = None
-    if head_ll is not None:
-        w1l, b1l, w3l, b3l = head_ll
-        wpl1, wpl2 = _ll_chain_pack(w1l, w3l)
-        b1l_c = _c(b1l.detach())
-        a.ll_wp1, a.ll_bias1, a.ll_wp2 = ptr(wpl1), ptr(b1l_c), ptr(wpl2)
-        keep += [wpl1, wpl2, b1l_c]
-    check(l.wmd_head_fused_fwd(C.byref(a), current_stream()), "wmd_head_fused_fwd")
-    return dict(t=t, B=B, H=H, W=W, b3p=b3p, b3n=b3n, b3l=b3l, has_ll=head_ll is not None, keep=keep)
+    a, item = _head_fused_args(x, head_p, head_n, head_ll)
+    check(_lib.lib().wmd_head_fused_fwd(C.byref(a), current_stream()), "wmd_head_fused_fwd")
+    return item
 
 
 def head_shiftsum_chain_nograd(items, scales, disp_scales, scale_ll=1.0, yl=None, clamp01=True):
     """Completes up to three consecutive levels (coarse to fine; items from head_fused_gemm_nograd) in ONE launch
     (wmd_head_shiftsum_chain_fwd): per level -> (yh [B,1,3,H,W], out [B,1,2H,2W], disp, yl_ll or None)."""
-    l = _lib.lib()
-    n = len(items)
-    arr = (_lib.HeadShiftsumArgs * n)()
-    res = []
-    yl_c = _c(yl) if yl is not None else None   # held until after the launch: a dropped temporary's block could be handed to yh / out / disp below
-    for k, it in enumerate(items):
-        B, H, W = it["B"], it["H"], it["W"]
-        dev = it["t"].device
-        yh = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
-        out = torch.empty((B, 1, 2 * H, 2 * W), device=dev, dtype=torch.float32)
-        disp = torch.empty_like(out)
-        yl_ll = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if (k == 0 and it["has_ll"]) else None
-        if k == 0 and not it["has_ll"] and yl is None:
-            raise _lib.WmdError("head_shiftsum_chain_nograd: the first level needs its low-pass input (yl) or the low-pass head")
-        arr[k] = _lib.HeadShiftsumArgs(B=B, H=H, W=W, pad_mode=PAD["reflect"], scale=float(scales[k]), t=ptr(it["t"]), bias_p=ptr(it["b3p"]),
-                                       bias_n=ptr(it["b3n"]), yh=ptr(yh), yl=ptr(yl_c) if (k == 0 and yl_ll is None) else None, out=ptr(out),
-                                       disp=ptr(disp), disp_scale=float(disp_scales[k]), clamp01=int(clamp01),
-                                       bias_ll=ptr(it["b3l"]) if yl_ll is not None else None, scale_ll=float(scale_ll),
-                                       yl_out=ptr(yl_ll))
-        res.append((yh.unsqueeze(1), out, disp, yl_ll))
-    check(l.wmd_head_shiftsum_chain_fwd(arr, n, current_stream()), "wmd_head_shiftsum_chain_fwd")
-    del yl_c   # (the items' `keep` lists -- contiguous copies the GEMM launches read -- live in `items` until the caller drops them)
-    return res
+    arr, res, _yl_c = _shiftsum_args(items, scales, disp_scales, yl, scale_ll, clamp01)
+    check(_lib.lib().wmd_head_shiftsum_chain_fwd(arr, len(items), current_stream()), "wmd_head_shiftsum_chain_fwd")
+    return res   # (the items' `keep` lists -- contiguous copies the GEMM launches read -- live in `items` until the caller drops them)
 
 
 _HEAD_PYRAMID = os.environ.get("WMD_HEAD_PYRAMID", "1") != "0"   # 0: the coarser levels' completions as a launch of their own
@@ -1086,7 +1062,7 @@ _HEAD_PYRAMID = os.environ.get("WMD_HEAD_PYRAMID", "1") != "0"   # 0: the coarse
 
 def head_level_pyramid_supported(C_, B, H, W):
     """Dense inference: can the C = 32 level run its heads + synthesis AND the coarser levels' completions in one launch?"""
-    return _HEAD_PYRAMID and not _TWO_LAUNCH_HEAD and os.environ.get("WMD_HEAD_STREAM", "1") != "0" and \
+    return _HEAD_PYRAMID and os.environ.get("WMD_HEAD_STREAM", "1") != "0" and \
         _lib.lib().wmd_head_level_pyramid_supported(int(C_), int(B), int(H), int(W)) >= (1 if os.environ.get("WMD_HEAD_PYRAMID") == "2" else 2)
 
 
@@ -1095,40 +1071,15 @@ def head_level_pyramid_nograd(x, head_p, head_n, scale, disp_scale, items, scale
     head_fused_gemm[_multi]_nograd, coarse to fine) in ONE launch -- the streaming kernel's epilogue waves complete the coarser
     levels over each unit's footprint first and hand the low-pass tiles down through LDS.  -> ([(yh, out, disp, yl_ll or None) per
     coarse level], (yh, out, disp) of this level); same bits as head_shiftsum_chain_nograd + head_fused_level_nograd."""
-    l = _lib.lib()
     x = _c(x)
     B, Cc, H, W = x.shape
-    n = len(items)
-    arr = (_lib.HeadShiftsumArgs * n)()
-    res = []
-    yl_c = _c(yl) if yl is not None else None
-    for k, it in enumerate(items):
-        Bk, Hk, Wk = it["B"], it["H"], it["W"]
-        dev = it["t"].device
-        yh = torch.empty((Bk, 3, Hk, Wk), device=dev, dtype=torch.float32)
-        out = torch.empty((Bk, 1, 2 * Hk, 2 * Wk), device=dev, dtype=torch.float32)
-        disp = torch.empty_like(out)
-        yl_ll = torch.empty((Bk, 1, Hk, Wk), device=dev, dtype=torch.float32) if (k == 0 and it["has_ll"]) else None
-        if k == 0 and not it["has_ll"] and yl is None:
-            raise _lib.WmdError("head_level_pyramid_nograd: the first coarse level needs its low-pass input (yl) or the low-pass head")
-        arr[k] = _lib.HeadShiftsumArgs(B=Bk, H=Hk, W=Wk, pad_mode=PAD["reflect"], scale=float(scales[k]), t=ptr(it["t"]), bias_p=ptr(it["b3p"]),
-                                       bias_n=ptr(it["b3n"]), yh=ptr(yh), yl=ptr(yl_c) if (k == 0 and yl_ll is None) else None, out=ptr(out),
-                                       disp=ptr(disp), disp_scale=float(disp_scales[k]), clamp01=int(clamp01),
-                                       bias_ll=ptr(it["b3l"]) if yl_ll is not None else None, scale_ll=float(scale_ll),
-                                       yl_out=ptr(yl_ll))
-        res.append((yh.unsqueeze(1), out, disp, yl_ll))
-    (w1p, b1p, w3p, b3p), (w1n, b1n, w3n, b3n) = head_p, head_n
-    wp1, bias1 = stacked_pack([w1p, w1n], [b1p, b1n])
-    wp2 = _tap_partial_pack(w3p, w3n)
-    yh1 = torch.empty((B, 3, H, W), device=x.device, dtype=torch.float32)
-    out1 = torch.empty((B, 1, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-    disp1 = torch.empty_like(out1) if disp_scale is not None else None
-    a = _lib.HeadLevelArgs(B=B, H=H, W=W, C=Cc, pad_mode=PAD["reflect"], slope=0.1, scale=float(scale), x=ptr(x),
-                           wp1=ptr(wp1), bias1=ptr(bias1), wp2=ptr(wp2), bias_p=ptr(b3p), bias_n=ptr(b3n), yh=ptr(yh1),
-                           yl=None, out=ptr(out1), disp=ptr(disp1), disp_scale=float(disp_scale or 1.0), clamp01=int(clamp01), yh_mask=None)
-    check(l.wmd_head_level_pyramid_fwd(C.byref(a), arr, n, current_stream()), "wmd_head_level_pyramid_fwd")
-    del yl_c
-    return res, (yh1.unsqueeze(1), out1, disp1)
+    arr, res, _yl_c = _shiftsum_args(items, scales, disp_scales, yl, scale_ll, clamp01)
+    yh = torch.empty((B, 3, H, W), device=x.device, dtype=torch.float32)
+    out = torch.empty((B, 1, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
+    disp = torch.empty_like(out) if disp_scale is not None else None
+    a, _keep = _head_level_args(x, head_p, head_n, scale, yh, out, disp, disp_scale, clamp01)
+    check(_lib.lib().wmd_head_level_pyramid_fwd(C.byref(a), arr, len(items), current_stream()), "wmd_head_level_pyramid_fwd")
+    return res, (yh.unsqueeze(1), out, disp)
 
 
 _TRAIN_FUSED = os.environ.get("WMD_TRAIN_FUSED_HEADS", "1") != "0"   # 0: training forward of the heads on _StackedHeadsFn + idwt_haar
@@ -1139,13 +1090,13 @@ def fused_train_supported(C_, H, W, has_ll):
     """Can the training forward of a level's heads run on the fused inference kernels (_FusedLevelFn)?  They must be able to
     write the 1x1 outputs: the one-launch kernel (C = 32, no low-pass head) or the chained kernel (C = 64 / 128 / 256, planes of
     a multiple of 4 pixels; the low-pass head only folded into the C = 256 launch)."""
-    if not _TRAIN_FUSED or _TWO_LAUNCH_HEAD:
+    if not _TRAIN_FUSED:
         return False
     if bool(_lib.lib().wmd_head_level_supported(int(C_))):
         return not has_ll
     if not _HEAD_CHAIN_ON or int(C_) not in (64, 128, 256) or (H * W) % 4:
         return False
-    return (not has_ll) or (int(C_) == 256 and _LL_FOLD and _LL_MERGE)
+    return (not has_ll) or int(C_) == 256
 
 
 class _FusedLevelFn(torch.autograd.Function):
