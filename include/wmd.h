@@ -207,6 +207,37 @@ int wmd_conv_pack_many(const wmd_pack_item* items, int n, void* stream);
 int wmd_conv_num_configs(void);
 const char* wmd_conv_config_name(int i);
 
+/* ------------------------------------------------------------------ *
+ * Opt-in reduced precision for the 3x3 trunk convolutions: bf16 MFMA (v_mfma_f32_32x32x16_bf16), fp32 accumulate.
+ * Tensors stay fp32 NCHW exactly as for wmd_conv_fwd; the operands are rounded on load.  With q(v) = fp32 -> bf16
+ * round-to-nearest-even:
+ *   terms = 1   y = act( sum_k q(x_k) q(w_k) + bias )                                   ~3e-3 of the tensor scale end to end
+ *   terms = 3   y = act( sum_k [ q(x_k) q(w_k) + q(x_k) q(w_k - q(w_k)) + q(x_k - q(x_k)) q(w_k) ] + bias )      ~1e-5
+ * (products of two bf16 values are exact in fp32; the sum is fp32 in an unspecified but fixed order: a launch is
+ * bit-repeatable, there are no float atomics).  Same fusion as wmd_conv_fwd: nearest x2 upsample of x1, concat with x2, border
+ * addressing, bias, activation.  wmd_conv_args is reused unchanged: wp = the image of wmd_conv_bf16_pack_weights, wp_wino is
+ * ignored, tune_cfg = k > 0 forces entry k-1 of the table below (every entry runs every supported problem), tune_ksplit = k
+ * (either sign) forces min(|k|, Cin/16) slices of the Cin reduction, summed in slice order by a second-stage kernel.
+ * Supported (everything else WMD_ERR_UNSUPPORTED before any launch; wmd_conv_bf16_supported answers without a HIP call):
+ *   ksize = 3; pad ZERO or REFLECT; C1 % 16 == 0, C2 % 16 == 0, Cout % 32 == 0; gate, in_mask, out_mask, out_tiles NULL;
+ *   tune_cfg in 0 .. wmd_conv_bf16_num_configs().
+ * Packed weight image: bf16 in MFMA fragment order, plane q(w), then for terms = 3 plane q(w - q(w)):
+ *   wmd_conv_bf16_packed_weight_bytes = 2 * 9 * Cout * Cin * (terms == 3 ? 2 : 1)      (0 unless Cout % 32 == 0, Cin % 16 == 0
+ *   and terms is 1 or 3).
+ * Workspace: a split needs slices * B*Cout*H*W floats.  wmd_conv_bf16_workspace_floats is what the library's choice (or the
+ * forced split) wants; the library's own split is skipped when the workspace is NULL or smaller, a forced one is refused
+ * (WMD_ERR_WORKSPACE).
+ * wmd_conv_bf16_config_name: "conv_bf16_kernel<TH,TW,MR,NR>" (pixel tile TH x TW, MR x NR 32x32 MFMA tiles per wave); the
+ * profiler reports launches as "conv_bf16_kernel<TH,TW,MR,NR,TERMS>" with mfma_flops = TERMS x flops.
+ * ------------------------------------------------------------------ */
+size_t wmd_conv_bf16_packed_weight_bytes(int Cout, int Cin, int terms);
+int wmd_conv_bf16_pack_weights(const float* w, void* wp, int Cout, int Cin, int terms, void* stream);
+int wmd_conv_bf16_supported(const wmd_conv_args* args, int terms);
+size_t wmd_conv_bf16_workspace_floats(const wmd_conv_args* args, int terms);
+int wmd_conv_bf16_fwd(const wmd_conv_args* args, int terms, void* stream);
+int wmd_conv_bf16_num_configs(void);
+const char* wmd_conv_bf16_config_name(int i);
+
 /* dz = dy * act'(y)  (y = the activation OUTPUT saved by the forward). In place allowed. */
 int wmd_act_bwd(const float* dy, const float* y, float* dz, size_t n, int act, float slope, void* stream);
 

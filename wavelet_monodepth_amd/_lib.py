@@ -173,6 +173,13 @@ SIGNATURES = {
     "wmd_conv_fwd_workspace_floats": (C.c_size_t, [C.POINTER(ConvArgs)]),
     "wmd_conv_num_configs": (C.c_int, []),
     "wmd_conv_config_name": (C.c_char_p, [C.c_int]),
+    "wmd_conv_bf16_packed_weight_bytes": (C.c_size_t, [C.c_int] * 3),
+    "wmd_conv_bf16_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "wmd_conv_bf16_supported": (C.c_int, [C.POINTER(ConvArgs), C.c_int]),
+    "wmd_conv_bf16_workspace_floats": (C.c_size_t, [C.POINTER(ConvArgs), C.c_int]),
+    "wmd_conv_bf16_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.c_void_p]),
+    "wmd_conv_bf16_num_configs": (C.c_int, []),
+    "wmd_conv_bf16_config_name": (C.c_char_p, [C.c_int]),
     "wmd_act_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_size_t, C.c_int, C.c_float, C.c_void_p]),
     "wmd_conv_dgrad_workspace_floats": (C.c_size_t, [C.POINTER(ConvDgradArgs)]),
     "wmd_conv_dgrad": (C.c_int, [C.POINTER(ConvDgradArgs), C.c_void_p]),

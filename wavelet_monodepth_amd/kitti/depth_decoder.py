@@ -73,6 +73,47 @@ class DepthWaveProgressiveDecoder(nn.Module):
         self.static_route = {"buffers": 0, "pointer_replay": 0, "copy": 0}
         self._segment_captures = 0
         self._segments = {}
+        # opt-in reduced precision of the eight trunk convolutions (set_precision): "fp32" | "bf16x3" | "bf16"
+        self.trunk_precision = "fp32"
+        self._trunk_plan = {}          # layer key -> mode of the current forward
+        self._trunk_plans = {}         # (mode, feature shapes) -> plan
+
+    # -- trunk precision -----------------------------------------------------------------------
+    def set_precision(self, mode):
+        """Inference precision of the trunk convolutions upconv(i, 0..1): "fp32" (default), "bf16x3" (operands split into
+        bf16 head + tail, three bf16 MFMA products: inside the 1e-4 parity contract) or "bf16" (operands rounded to bf16:
+        ~3e-3, outside it).  Heads, IDWT and every tensor stay fp32.  A layer the bf16 operator does not take (channel counts
+        that are not multiples of 16 / 32) runs in fp32, see trunk_precision_report(); with autograd enabled the fp32 path
+        runs regardless.  Captured graphs are keyed on the mode."""
+        if mode not in ("fp32",) + tuple(ops.PRECISION_TERMS):
+            raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16', got %r" % (mode,))
+        self.trunk_precision = mode
+        return self
+
+    def trunk_precision_report(self):
+        """{("upconv", i, j): "bf16x3" | "bf16" | "fp32"}: what each trunk layer ran in during the last forward."""
+        return {k: (v or "fp32") for k, v in self._trunk_plan.items()}
+
+    def _plan_precision(self, feats):
+        mode = self.trunk_precision if not torch.is_grad_enabled() else "fp32"
+        key = (mode,) + tuple(tuple(f.shape) for f in feats)
+        plan = self._trunk_plans.get(key)
+        if plan is None:
+            plan = {}
+            B, cx, h, w = feats[-1].shape
+            for i in range(4, 0, -1):
+                cd = int(self.num_ch_dec[i])
+                c2 = int(feats[i - 1].shape[1]) if self.use_skips else 0
+                shapes = {0: (B, h, w, cx, 1, 0, cd), 1: (B, 2 * h, 2 * w, cd, 2, c2, cd)}
+                for j in (0, 1):
+                    ok = mode != "fp32" and ops.conv3x3_bf16_supported(*shapes[j], pad="reflect", terms=ops.PRECISION_TERMS[mode])
+                    plan[("upconv", i, j)] = mode if ok else None
+                cx, h, w = cd, 2 * h, 2 * w
+            if len(self._trunk_plans) >= 16:
+                self._trunk_plans.clear()
+            self._trunk_plans[key] = plan
+        self._trunk_plan = plan
+        return plan
 
     # -- pieces ------------------------------------------------------------------------------
     def _head_params(self, i, j):
@@ -232,13 +273,15 @@ class DepthWaveProgressiveDecoder(nn.Module):
         if edge is not None and torch.is_grad_enabled():
             input_features[-1], edge = edge.activate(), None        # training: the ordinary path on the activated tensor
         self._edge = edge
+        self._plan_precision(input_features)
         if self._graph_mode and not torch.is_grad_enabled():
             input_features, retain = self._bound(input_features)
             if self.two_stream_graphs and edge is None and retain:
                 self.outputs = self._forward_two_streams(input_features)
             else:
                 self.outputs = self._graphs.run(self._forward_impl, input_features, self.parameters(),
-                                                extra_key=("edge",) + edge.key() if edge is not None else (), retain_inputs=retain)
+                                                extra_key=(("edge",) + edge.key() if edge is not None else ()) + (self.trunk_precision,),
+                                                retain_inputs=retain)
             return self.outputs
         return self._forward_impl(input_features)
 
@@ -252,7 +295,7 @@ class DepthWaveProgressiveDecoder(nn.Module):
     # stream share a memory pool (they replay in capture order); the two streams use different pools, so a buffer freed
     # during one capture can never be handed to a segment that runs concurrently; tensors that cross streams stay alive.
     def _forward_two_streams(self, input_features):
-        key = tuple((t.data_ptr(), tuple(t.shape)) for t in input_features) + tuple((p.data_ptr(), p._version) for p in self.parameters()) + (ops.pack_generation(),)
+        key = tuple((t.data_ptr(), tuple(t.shape)) for t in input_features) + tuple((p.data_ptr(), p._version) for p in self.parameters()) + (ops.pack_generation(), self.trunk_precision)
         ent = self._segments.get(key)
         if ent is None:
             if len(self._segments) >= 4:
@@ -289,9 +332,9 @@ class DepthWaveProgressiveDecoder(nn.Module):
         for i in range(4, 0, -1):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool_main):
-                x = self.convs[("upconv", i, 0)](x)
+                x = self.convs[("upconv", i, 0)](x, precision=self._trunk_plan[("upconv", i, 0)])
                 skip = feats[i - 1] if self.use_skips else None
-                x = self.convs[("upconv", i, 1)](x, skip=skip, up=2)
+                x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, precision=self._trunk_plan[("upconv", i, 1)])
             trunk[i] = g
             keep.append(x)
             g = torch.cuda.CUDAGraph()
@@ -343,13 +386,15 @@ class DepthWaveProgressiveDecoder(nn.Module):
         chain_multi, chain, pyramid = self._dense_route(input_features, edge)
         scales, disp_scales = [2.0 ** (k - 1) for k in (4, 3, 2)], [1.0 / 2 ** (k - 1) for k in (4, 3, 2)]
         pending, deferred = [], []
+        prec = self._plan_precision(input_features)     # per trunk layer: None (fp32 operators) or the bf16 mode it runs in
         for i in range(4, 0, -1):
             if i == 4 and edge is not None:
-                x = self.convs[("upconv", 4, 0)](x, x1_pre=edge.pre())      # ReLU (+ affine) of the encoder's last block on load
+                x = self.convs[("upconv", 4, 0)](x, x1_pre=edge.pre(), precision=prec[("upconv", 4, 0)])      # ReLU (+ affine) of the encoder's last block on load
             else:
-                x = self.convs[("upconv", i, 0)](x, x1_gate=elu if i < 4 else None, grad_is_dz=elu is not None)
+                x = self.convs[("upconv", i, 0)](x, x1_gate=elu if i < 4 else None, grad_is_dz=elu is not None, precision=prec[("upconv", i, 0)])
             skip = input_features[i - 1] if (self.use_skips and i > 0) else None
-            x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, x1_gate=elu, grad_is_dz=elu is not None)  # fused upsample + concat
+            x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, x1_gate=elu, grad_is_dz=elu is not None,
+                                             precision=prec[("upconv", i, 1)])  # fused upsample + concat
             if chain and i >= 2:        # levels 4..2: first stage now or deferred, then one completion launch (see _dense_route)
                 level = (x, self._head_params(i, 1), self._head_params(i, -1), self._head_params(i, 0) if i == 4 else None)
                 if chain_multi:

@@ -85,10 +85,17 @@ class Conv3x3(nn.Module):
         self.pad_mode = "reflect" if use_refl else "zero"
         self.conv = nn.Conv2d(int(in_channels), int(out_channels), 3, stride=stride, bias=use_bias)
 
-    def forward(self, x, skip=None, up=1, act="none", slope=0.0, x1_gate=None, grad_is_dz=False, x1_pre=None):
+    def forward(self, x, skip=None, up=1, act="none", slope=0.0, x1_gate=None, grad_is_dz=False, x1_pre=None, precision=None):
+        # precision: None / "fp32" = the fp32 operators; "bf16x3" / "bf16" = ops.conv3x3_bf16_nograd (inference, opt-in)
         if x1_pre is not None:      # encoder edge (inference): x is a pre-activation, activated on load
             assert skip is None
-            return ops.conv2d_pre_activated(x, x1_pre, self.conv.weight, self.conv.bias, up1=up, pad=self.pad_mode, act=act, slope=slope)
+            return ops.conv2d_pre_activated(x, x1_pre, self.conv.weight, self.conv.bias, up1=up, pad=self.pad_mode, act=act, slope=slope,
+                                            precision=precision)
+        if precision not in (None, "fp32"):
+            if precision not in ops.PRECISION_TERMS:
+                raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16', got %r" % (precision,))
+            return ops.conv3x3_bf16_nograd(x, self.conv.weight, self.conv.bias, x2=skip, up1=up, pad=self.pad_mode, act=act,
+                                           slope=slope, terms=ops.PRECISION_TERMS[precision])
         return ops.conv2d_fused(x, self.conv.weight, self.conv.bias, x2=skip, up1=up, pad=self.pad_mode, act=act,
                                 slope=slope, x1_gate=x1_gate, grad_is_dz=grad_is_dz)
 
@@ -120,11 +127,13 @@ class ConvBlock(nn.Module):
             raise NotImplementedError
         self.kernel_size = kernel_size
 
-    def forward(self, x, skip=None, up=1, x1_gate=None, grad_is_dz=False, x1_pre=None):
+    def forward(self, x, skip=None, up=1, x1_gate=None, grad_is_dz=False, x1_pre=None, precision=None):
         if self.kernel_size == 3:
-            return self.conv(x, skip=skip, up=up, act="elu", x1_gate=x1_gate, grad_is_dz=grad_is_dz, x1_pre=x1_pre)
+            return self.conv(x, skip=skip, up=up, act="elu", x1_gate=x1_gate, grad_is_dz=grad_is_dz, x1_pre=x1_pre, precision=precision)
         if x1_pre is not None:
             raise NotImplementedError("the encoder edge feeds a 3x3 ConvBlock")
+        if precision not in (None, "fp32"):
+            raise NotImplementedError("reduced precision is implemented for 3x3 blocks")
         return self.conv(x, act="elu", x1_gate=x1_gate, grad_is_dz=grad_is_dz)
 
 

@@ -343,7 +343,7 @@ def _wgrad_launch(a, device):
     check(launch(cfg), "wmd_conv_wgrad")
 
 
-def conv2d_pre_activated(x1, x1_pre, weight, bias=None, up1=1, pad="reflect", act="none", slope=0.0):
+def conv2d_pre_activated(x1, x1_pre, weight, bias=None, up1=1, pad="reflect", act="none", slope=0.0, precision=None):
     """conv2d_fused for an x1 that is still a PRE-activation (the encoder edge, layers.DeferredActivation):
     act( conv( pad( nearest_up( pre(x1) ) ) ) + bias ) with pre(v)[c] = pre_act(v * scale[c] + shift[c]); x1_pre = (scale, shift,
     act, slope).  Round 3 applied pre() on load inside dedicated instantiations of the direct kernel; that form lost the tuned
@@ -370,6 +370,8 @@ def conv2d_pre_activated(x1, x1_pre, weight, bias=None, up1=1, pad="reflect", ac
             v = v + psh.view(1, -1, 1, 1)
         if pact == "leaky":
             v = torch.relu(v) if pslope == 0.0 else torch.nn.functional.leaky_relu(v, pslope)
+        if precision in PRECISION_TERMS:    # the activated edge on the bf16 operator (opt-in trunk precision)
+            return conv3x3_bf16_nograd(v, weight, bias, up1=up1, pad=pad, act=act, slope=slope, terms=PRECISION_TERMS[precision])
         return conv2d_fused(v, weight, bias, up1=up1, pad=pad, act=act, slope=slope)
 
 
@@ -387,6 +389,103 @@ def conv2d_fused(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none
     if weight.shape[1] != cin:
         raise _lib.WmdError("weight expects %d input channels, got %d" % (weight.shape[1], cin))
     return _ConvFn.apply(x1, x2, weight, bias, ksize, pad, act, slope, up1, x1_gate, grad_is_dz)
+
+
+# ---------------------------------------------------------------------------------------------
+# opt-in reduced precision: 3x3 convolution on bf16 MFMAs (wmd_conv_bf16_fwd)
+# ---------------------------------------------------------------------------------------------
+
+PRECISION_TERMS = {"bf16x3": 3, "bf16": 1}   # trunk precision mode -> bf16 products per k-step ("fp32": the ordinary operators)
+_BF16_KSPLITS = (1, 2, 3, 4, 6, 8)
+_BF16_NAMES = None
+
+
+def pack_weights_bf16(weight, terms):
+    """[Cout,Cin,3,3] -> bf16 fragment image of wmd_conv_bf16_pack_weights (terms = 3: head plane + tail plane); memoised on
+    the weight like pack_weights (own slot per `terms`, same tag, same invalidate_packs generation, no memo while capturing)."""
+    l = _lib.lib()
+    tag = (weight._version, weight.data_ptr(), weight.device, _pack_generation[0])
+    slot = "_wmd_pack_b%d" % terms
+    if _PACK_CACHE:
+        hit = getattr(weight, slot, None)
+        if hit is not None and hit[0] == tag:
+            return hit[1]
+    cout, cin = weight.shape[:2]
+    n = l.wmd_conv_bf16_packed_weight_bytes(cout, cin, terms)
+    if n == 0 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.WmdError("no bf16 weight image for a %s filter with terms=%r" % (tuple(weight.shape), terms))
+    wp = torch.empty(n, device=weight.device, dtype=torch.uint8)
+    check(l.wmd_conv_bf16_pack_weights(ptr(_c(weight.detach())), ptr(wp), cout, cin, terms, current_stream()),
+          "wmd_conv_bf16_pack_weights")
+    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
+        try:
+            setattr(weight, slot, (tag, wp))
+        except AttributeError:
+            pass
+    return wp
+
+
+def conv3x3_bf16_supported(B, H, W, C1, up1, C2, cout, pad="reflect", terms=3):
+    """Does wmd_conv_bf16_fwd take this problem?  Shapes only, no GPU call (the decoders ask per trunk layer)."""
+    a = _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=3, pad_mode=PAD[pad], act=0, slope=0.0,
+                      x1=1, x2=1 if C2 else None, wp=1, bias=None, y=1, workspace=None, workspace_floats=0)
+    return bool(_lib.lib().wmd_conv_bf16_supported(C.byref(a), terms))
+
+
+def conv3x3_bf16_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none", slope=0.0, terms=3):
+    """act( conv3x3( pad( cat[ nearest_up(x1, up1), x2 ] ) ) + bias ) with both operands rounded to bf16 (terms = 1) or split
+    into bf16 head + tail, three products (terms = 3), fp32 accumulate -- the contract in include/wmd.h.  fp32 tensors in and
+    out.  Inference operator; a problem the kernel does not take raises (it is never computed in fp32 instead)."""
+    _require_gpu(x1, x2, weight, bias)
+    if torch.is_grad_enabled() and (x1.requires_grad or weight.requires_grad or (x2 is not None and x2.requires_grad)
+                                    or (bias is not None and bias.requires_grad)):
+        raise _lib.WmdError("conv3x3_bf16_nograd is an inference operator (use conv2d_fused to train)")
+    if terms not in (1, 3):
+        raise _lib.WmdError("terms must be 1 or 3, got %r" % (terms,))
+    global _BF16_NAMES
+    l = _lib.lib()
+    x1, x2, bias = _c(x1), _c(x2), _c(bias)
+    B, C1 = x1.shape[0], x1.shape[1]
+    H, W = x1.shape[2] * up1, x1.shape[3] * up1
+    C2 = 0 if x2 is None else x2.shape[1]
+    cout = weight.shape[0]
+    if weight.shape[1] != C1 + C2:
+        raise _lib.WmdError("weight expects %d input channels, got %d" % (weight.shape[1], C1 + C2))
+    if x2 is not None and (x2.shape[0] != B or x2.shape[2] != H or x2.shape[3] != W):
+        raise _lib.WmdError("skip tensor %s does not match upsampled input %s" % (tuple(x2.shape), (B, C1, H, W)))
+    a = _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=weight.shape[-1], pad_mode=PAD[pad], act=ACT[act],
+                      slope=float(slope), x1=ptr(x1), x2=ptr(x2), wp=1, bias=ptr(bias), y=1, workspace=None,
+                      workspace_floats=0, tune_cfg=0, tune_ksplit=0)
+    if not l.wmd_conv_bf16_supported(C.byref(a), terms):
+        raise _lib.WmdError("wmd_conv_bf16_fwd does not take this problem: %s" % l.wmd_last_error().decode())
+    wp = pack_weights_bf16(weight, terms)
+    y = torch.empty((B, cout, H, W), device=x1.device, dtype=torch.float32)
+    a.wp, a.y = ptr(wp), ptr(y)
+    stream = current_stream()
+    keep = []
+
+    def launch(choice):
+        a.tune_cfg, a.tune_ksplit = choice
+        a.workspace, a.workspace_floats = None, 0
+        n = l.wmd_conv_bf16_workspace_floats(C.byref(a), terms)
+        if n:
+            ws = torch.empty(n, device=x1.device, dtype=torch.float32)
+            keep[:] = [ws]
+            a.workspace, a.workspace_floats = ptr(ws), n
+        return l.wmd_conv_bf16_fwd(C.byref(a), terms, stream)
+
+    choice = (0, 0)
+    if tuner.enabled:
+        if _BF16_NAMES is None:
+            _BF16_NAMES = [l.wmd_conv_bf16_config_name(i).decode() for i in range(l.wmd_conv_bf16_num_configs())]
+        # keys of their own: no entry of a cache written for the fp32 operators is read or changed by this path
+        key = "conv16|%d|%d|%d|%d|%d|%d|%d|%d" % (B, H, W, C1, up1, C2, cout, terms)
+        nchunks = (C1 + C2) // 16
+        cands = [("library", (0, 0))] + [("%s|%d" % (n, ks), (i + 1, ks)) for i, n in enumerate(_BF16_NAMES)
+                                         for ks in _BF16_KSPLITS if ks <= max(1, nchunks // 2)]
+        choice = tuner.choose(key, cands, launch)
+    check(launch(choice), "wmd_conv_bf16_fwd")
+    return y
 
 
 class _DwConvFn(torch.autograd.Function):
