@@ -618,6 +618,52 @@ def test_tuner_choose_picks_the_fastest_valid_candidate_and_caches_its_label(mon
     assert tuner.choose("wgrad|other", cands, launch) == 0
 
 
+def test_weight_image_memo_states_the_staleness_rule_once(monkeypatch):
+    """ops._memo / ops._pack_tag (every packed weight image goes through them): a hit while the tagged tensors are unchanged; a
+    miss after an in-place update of any of them and after invalidate_packs(); a stream capture reads the memo and never
+    stores; a build that raises stores nothing; an owner that takes no attributes and WMD_PACK_CACHE=0 build every time."""
+    import torch
+    from wavelet_monodepth_amd import ops
+    capturing = [False]
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
+    monkeypatch.setattr(ops, "_PACK_CACHE", True)
+    w, b = torch.zeros(4, 4, 3, 3), torch.ones(4)
+    builds = []
+
+    def build():
+        builds.append(1)
+        return len(builds), "image"
+
+    def get(owner=w):
+        return ops._memo(owner, "_wmd_pack_test", ops._pack_tag(w, b), build)
+
+    assert ops._pack_tag(w)[0] == w._version and ops._pack_tag(w) != ops._pack_tag(w.clone())
+    assert get() == (1, "image") and get() == (1, "image") and len(builds) == 1              # hit
+    assert w._wmd_pack_test == (ops._pack_tag(w, b), 1, "image")                             # stored as (tag, *payload)
+    with torch.no_grad():
+        b.add_(1.0)                                                                          # in-place update of a tagged tensor
+    assert get() == (2, "image") and get() == (2, "image") and len(builds) == 2
+    ops.invalidate_packs()
+    assert get() == (3, "image") and get() == (3, "image") and len(builds) == 3
+    capturing[0] = True
+    assert get() == (3, "image") and len(builds) == 3                                        # the memo is read in a capture ...
+    with torch.no_grad():
+        w.mul_(2.0)
+    assert get() == (4, "image") and get() == (5, "image") and w._wmd_pack_test[1] == 3      # ... and never stored into
+    capturing[0] = False
+    assert get() == (6, "image") and get() == (6, "image") and w._wmd_pack_test[1] == 6
+
+    def refuse():
+        raise ops._lib.WmdError("no image for this filter")
+
+    with pytest.raises(ops._lib.WmdError):
+        ops._memo(w, "_wmd_pack_refused", ops._pack_tag(w), refuse)
+    assert not hasattr(w, "_wmd_pack_refused")
+    assert get(object()) == (7, "image") and get(object()) == (8, "image")                   # no attribute can be set: no memo
+    monkeypatch.setattr(ops, "_PACK_CACHE", False)
+    assert get() == (9, "image") and get() == (10, "image") and w._wmd_pack_test[1] == 6     # switched off: neither read nor stored
+
+
 def test_train_step_graph_refuses_an_optimizer_that_cannot_be_captured():
     import torch
     from wavelet_monodepth_amd.graphs import TrainStepGraph

@@ -10,7 +10,9 @@ Each function mirrors one reference operator group (file:line under /root/refere
   dwt_haar       DWT(J, "haar", "reflect") on even sizes (NYUv2/train.py:258,289)
 All of them are differentiable (torch.autograd.Function with hand-written HIP backward kernels).
 """
+import contextlib
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -35,10 +37,33 @@ def _c(t):
 
 
 # ---------------------------------------------------------------------------------------------
+# switches (environment, read once at import; tests and tools may assign the globals afterwards)
+# ---------------------------------------------------------------------------------------------
+
+_PACK_CACHE = os.environ.get("WMD_PACK_CACHE", "1") != "0"     # 0: no weight image is memoised on its tensor (_memo)
+_WINOGRAD = os.environ.get("WMD_WINOGRAD", "1") != "0"         # 0: no Winograd weight images, the 3x3 layers stay on the direct kernels
+_PREPACK = os.environ.get("WMD_PREPACK", "1") != "0"           # 0: every convolution packs for itself (prepack does nothing)
+_HEAD_BWD = os.environ.get("WMD_HEAD_BWD", "1") != "0"                 # 0: 3x3 head backward on the generic dgrad / wgrad kernels
+_HEAD_BWD_MERGED = os.environ.get("WMD_HEAD_BWD_MERGED", "1") != "0"   # 0: wmd_head3x3_bwd + wmd_head1x1_bwd as separate launch sets
+_HEAD_BWD_MIN_PIXELS = int(os.environ.get("WMD_HEAD_BWD_MIN_PIXELS", "16384"))   # B*H*W from which the 3x3 stage runs on wmd_head3x3_bwd
+_HEAD_BWD1_MIN_PIXELS = int(os.environ.get("WMD_HEAD_BWD1_MIN_PIXELS", "196608"))     # same for the 1x1 stage (wmd_head1x1_bwd):
+# its kernels walk the whole channel sum per 64-pixel wave tile and only win where a level has thousands of tiles (the finest one)
+_SHIFTSUM_CHAIN = os.environ.get("WMD_SHIFTSUM_CHAIN", "1") != "0"   # 0: one wmd_head_shiftsum_fwd launch per level
+# ... up to this many pixels at the finest chained level: the single launch removes two graph nodes from a latency-bound forward (one
+# frame 640x192: 0.221 -> 0.211 ms) but completes levels 4 and 3 from planes that have left the caches by then -- at batch 12
+# (92 160 pixels) the step measured 0.5 - 1 % slower with it (0.588 / 0.592 vs 0.585 / 0.584 ms medians, same box)
+_SHIFTSUM_CHAIN_MAX_PIXELS = int(os.environ.get("WMD_SHIFTSUM_CHAIN_MAX_PIXELS", "32768"))
+_HEAD_CHAIN_ON = os.environ.get("WMD_HEAD_CHAIN", "1") != "0"            # 0: no chained two-launch head kernels (C = 64 / 128 / 256)
+_HEAD_CHAIN_MULTI = os.environ.get("WMD_HEAD_CHAIN_MULTI", "1") != "0"   # 0: every level's first stage as a launch of its own
+_HEAD_PYRAMID = os.environ.get("WMD_HEAD_PYRAMID", "1") != "0"   # 0: the coarser levels' completions as a launch of their own
+_TRAIN_FUSED = os.environ.get("WMD_TRAIN_FUSED_HEADS", "1") != "0"   # 0: training forward of the heads on _StackedHeadsFn + idwt_haar
+# (head_level_pyramid_supported also reads WMD_HEAD_STREAM and WMD_HEAD_PYRAMID=2 on every call)
+
+
+# ---------------------------------------------------------------------------------------------
 # weight packing
 # ---------------------------------------------------------------------------------------------
 
-_PACK_CACHE = os.environ.get("WMD_PACK_CACHE", "1") != "0"
 _pack_generation = [0]
 
 
@@ -56,34 +81,47 @@ def invalidate_packs():
     _pack_generation[0] += 1
 
 
+def _pack_tag(*tensors):
+    """What an image built from `tensors` is current for: (version counter, storage pointer) of each, their device and the
+    invalidate_packs generation."""
+    tag = []
+    for t in tensors:
+        tag += (t._version, t.data_ptr())
+    return (*tag, tensors[0].device, _pack_generation[0])
+
+
+def _memo_hit(owner, slot, tag):
+    """The payload tuple memoised in `slot` of the tensor object `owner` if it was built for `tag`, else None."""
+    hit = getattr(owner, slot, None) if _PACK_CACHE else None
+    return hit[1:] if hit is not None and hit[0] == tag else None
+
+
+def _memo(owner, slot, tag, build):
+    """build() -> payload tuple, memoised ON the tensor object `owner` as (tag, *payload): reused while the tag matches (the
+    weights are constant: inference), rebuilt when it does not (optimizer step, load_state_dict, invalidate_packs).  A stream
+    capture reads the memo but never stores into it (the image built there lives in the graph's pool); an owner that takes
+    no attributes is packed every time; WMD_PACK_CACHE=0 disables the memo.  A build() that raises stores nothing."""
+    payload = _memo_hit(owner, slot, tag)
+    if payload is None:
+        payload = build()
+        if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
+            try:
+                setattr(owner, slot, (tag,) + payload)
+            except AttributeError:
+                pass
+    return payload
+
+
 def pack_weights(weight, dgrad=False):
-    """[Cout,Cin,k,k] -> MFMA fragment image (wmd_conv_pack_weights[_dgrad]).
-
-    The image is memoised ON the weight tensor object, keyed by its autograd version counter and storage
-    pointer, so it is rebuilt whenever the weight is updated in place (optimizer step, load_state_dict) and
-    reused while it is constant (inference).  WMD_PACK_CACHE=0 disables the memo."""
-    l = _lib.lib()
-    tag = (weight._version, weight.data_ptr(), weight.device, _pack_generation[0])
-    slot = "_wmd_pack_d" if dgrad else "_wmd_pack_f"
-    if _PACK_CACHE:
-        hit = getattr(weight, slot, None)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
-    cout, cin, k, _ = weight.shape
-    n = l.wmd_conv_packed_weight_floats(cout, cin, k)
-    wp = torch.empty(n, device=weight.device, dtype=torch.float32)
-    fn = l.wmd_conv_pack_weights_dgrad if dgrad else l.wmd_conv_pack_weights
-    check(fn(ptr(_c(weight.detach())), ptr(wp), cout, cin, k, current_stream()), "wmd_conv_pack_weights")
-    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
-        try:
-            setattr(weight, slot, (tag, wp))
-        except AttributeError:
-            pass
-    return wp
-
-
-_WINOGRAD = os.environ.get("WMD_WINOGRAD", "1") != "0"
-_PREPACK = os.environ.get("WMD_PREPACK", "1") != "0"
+    """[Cout,Cin,k,k] -> MFMA fragment image (wmd_conv_pack_weights[_dgrad]), memoised on the weight (_memo)."""
+    def build():
+        l = _lib.lib()
+        cout, cin, k, _ = weight.shape
+        wp = torch.empty(l.wmd_conv_packed_weight_floats(cout, cin, k), device=weight.device, dtype=torch.float32)
+        fn = l.wmd_conv_pack_weights_dgrad if dgrad else l.wmd_conv_pack_weights
+        check(fn(ptr(_c(weight.detach())), ptr(wp), cout, cin, k, current_stream()), "wmd_conv_pack_weights")
+        return (wp,)
+    return _memo(weight, "_wmd_pack_d" if dgrad else "_wmd_pack_f", _pack_tag(weight), build)[0]
 
 
 def pack_many(specs, with_buffer=False):
@@ -128,26 +166,20 @@ def prepack(weights, dgrad=True):
         if w is None or id(w) in seen or not w.is_cuda or w.dim() != 4 or w.shape[2] not in (1, 3):
             continue
         seen.add(id(w))
-        tag = (w._version, w.data_ptr(), w.device, _pack_generation[0])
-        k = w.shape[2]
+        tag = _pack_tag(w)
         slots = ["_wmd_pack_f"] + (["_wmd_pack_d"] if dgrad else [])
-        if k == 3 and _WINOGRAD:
+        if w.shape[2] == 3 and _WINOGRAD:
             slots += ["_wmd_pack_wf"] + (["_wmd_pack_wd"] if dgrad else [])
-        need = [sl for sl in slots if getattr(w, sl, (None,))[0] != tag]
+        need = [sl for sl in slots if _memo_hit(w, sl, tag) is None]
         if need:
             todo.append((w, tag, need))
     if not todo:
         return
     field = {"_wmd_pack_f": "fwd", "_wmd_pack_d": "dgrad", "_wmd_pack_wf": "wino_fwd", "_wmd_pack_wd": "wino_dgrad"}
     images = pack_many([(w, tuple(field[sl] for sl in need)) for w, _, need in todo])
-    views = [(w, sl, tag, img[field[sl]]) for (w, tag, need), img in zip(todo, images) for sl in need]
-    for w, sl, tag, view in views:
-        try:
-            setattr(w, sl, (tag, view))
-        except AttributeError:
-            pass
-
-
+    for (w, tag, need), img in zip(todo, images):
+        for sl in need:
+            _memo(w, sl, tag, lambda: (img[field[sl]],))
 
 
 def prepack_module(module):
@@ -169,24 +201,16 @@ def pack_weights_wino(weight, dgrad=False):
     pack_weights.  Returns None for other kernel sizes or when WMD_WINOGRAD=0."""
     if not _WINOGRAD or weight.shape[-1] != 3:
         return None
-    l = _lib.lib()
-    tag = (weight._version, weight.data_ptr(), weight.device, _pack_generation[0])
-    slot = "_wmd_pack_wd" if dgrad else "_wmd_pack_wf"
-    if _PACK_CACHE:
-        hit = getattr(weight, slot, None)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
-    cout, cin = weight.shape[:2]
-    rows, red = (cin, cout) if dgrad else (cout, cin)
-    wp = torch.empty(l.wmd_conv_packed_weight_floats_wino(rows, red), device=weight.device, dtype=torch.float32)
-    check(l.wmd_conv_pack_weights_wino(ptr(_c(weight.detach())), ptr(wp), cout, cin, int(dgrad), current_stream()),
-          "wmd_conv_pack_weights_wino")
-    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
-        try:
-            setattr(weight, slot, (tag, wp))
-        except AttributeError:
-            pass
-    return wp
+
+    def build():
+        l = _lib.lib()
+        cout, cin = weight.shape[:2]
+        rows, red = (cin, cout) if dgrad else (cout, cin)
+        wp = torch.empty(l.wmd_conv_packed_weight_floats_wino(rows, red), device=weight.device, dtype=torch.float32)
+        check(l.wmd_conv_pack_weights_wino(ptr(_c(weight.detach())), ptr(wp), cout, cin, int(dgrad), current_stream()),
+              "wmd_conv_pack_weights_wino")
+        return (wp,)
+    return _memo(weight, "_wmd_pack_wd" if dgrad else "_wmd_pack_wf", _pack_tag(weight), build)[0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -216,20 +240,10 @@ def _conv_fwd_raw(x1, x2, wp, bias, cout, ksize, pad, act, slope, up1, wp_wino=N
     if out_tiles is not None:
         tl, tc, th, tw = out_tiles
         a.out_tiles, a.out_tile_count, a.out_tile_h, a.out_tile_w = ptr(tl), ptr(tc), int(th), int(tw)
-    stream = current_stream()
-    keep = []
 
     def launch(cfg, ks):
         a.tune_cfg, a.tune_ksplit = cfg, ks
-        a.workspace, a.workspace_floats = None, 0
-        n = l.wmd_conv_fwd_workspace_floats(C.byref(a))
-        if n:
-            ws = torch.empty(n, device=x1.device, dtype=torch.float32)
-            keep[:] = [ws]   # same-stream reuse: the caching allocator may hand the block to the next candidate
-            a.workspace, a.workspace_floats = ptr(ws), n
-        elif ks > 1:
-            return -3
-        return l.wmd_conv_fwd(C.byref(a), stream)
+        return _launch_ws(a, l.wmd_conv_fwd_workspace_floats, l.wmd_conv_fwd, x1.device, False, split=ks > 1)
 
     choice = (0, 0)
     if tuner.enabled and out_tiles is None:     # (a work list fixes the tile shape; the K split is the device's decision)
@@ -238,29 +252,51 @@ def _conv_fwd_raw(x1, x2, wp, bias, cout, ksize, pad, act, slope, up1, wp_wino=N
             key += "|direct"   # a choice made with the Winograd configurations on offer must not be reused without them
         if out_mask is not None:
             key += "|tiles"    # block-sparse execution: its own (masked) instantiations, timed at full density (below)
-        choice = tuner.lookup(key)
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                choice = (0, 0)  # cannot time inside a capture: the library's cost model decides
-            elif out_mask is not None or in_mask is not None:
-                # The candidates are timed on ALL-ONES masks into a scratch output, not on the caller's masks: a first call with
-                # empty masks (every block returns at once, every configuration "takes" the same few microseconds) used to
-                # fix an arbitrary choice for the life of the process -- seen as 41 + 62 us unsplit level-2 launches after a
-                # test had tuned the same shape on an empty mask.  Full density is the reproducible worst case.
-                saved = (a.in_mask, a.out_mask, a.y)
-                ones = torch.ones((B, H, W), device=x1.device, dtype=torch.uint8)
-                scratch = torch.empty_like(y)
-                a.in_mask = ptr(ones) if in_mask is not None else None
-                a.out_mask = ptr(ones) if out_mask is not None else None
-                a.y = ptr(scratch)
-                try:
-                    choice = tuner.tune(key, 9 if ksize == 3 else 1, launch)
-                finally:
-                    a.in_mask, a.out_mask, a.y = saved
-            else:
-                choice = tuner.tune(key, 9 if ksize == 3 else 1, launch)
+        masked = out_mask is not None or in_mask is not None
+        choice = tuner.pick(key, 9 if ksize == 3 else 1, launch,
+                            (lambda: _full_density(a, y, in_mask is not None, out_mask is not None)) if masked else None)
     check(launch(*choice), "wmd_conv_fwd")
     return y
+
+
+@contextlib.contextmanager
+def _full_density(a, y, has_in, has_out):
+    """While the tuner times the candidates of a block-sparse convolution `a`: ALL-ONES masks and a scratch output instead of
+    the caller's.  A first call with empty masks (every block returns at once, every configuration "takes" the same few
+    microseconds) used to fix an arbitrary choice for the life of the process -- seen as 41 + 62 us unsplit level-2 launches
+    after a test had tuned the same shape on an empty mask.  Full density is the reproducible worst case."""
+    saved = (a.in_mask, a.out_mask, a.y)
+    ones = torch.ones((a.B, a.H, a.W), device=y.device, dtype=torch.uint8)
+    scratch = torch.empty_like(y)
+    a.in_mask, a.out_mask, a.y = ptr(ones) if has_in else None, ptr(ones) if has_out else None, ptr(scratch)
+    try:
+        yield
+    finally:
+        a.in_mask, a.out_mask, a.y = saved
+
+
+def _workspace(n, device, spare):
+    """The workspace tensor for a library request of n floats.  spare=False: none for n = 0 (the forward operators: their
+    planners read a null pointer as "no split possible"); spare=True: always at least one float (the backward operators)."""
+    return torch.empty(max(n, 1), device=device, dtype=torch.float32) if (n or spare) else None
+
+
+def _attach_ws(a, floats_fn, device, spare, *extra):
+    """Sizes the workspace of args struct `a` (floats_fn(a, *extra)) and attaches it; -> the tensor, to be held until the launch."""
+    a.workspace, a.workspace_floats = None, 0
+    n = floats_fn(C.byref(a), *extra)
+    ws = _workspace(n, device, spare)     # same-stream reuse: the caching allocator may hand the block to the next candidate
+    a.workspace, a.workspace_floats = ptr(ws), n
+    return ws
+
+
+def _launch_ws(a, floats_fn, run_fn, device, spare, *extra, split=False):
+    """_attach_ws, then run_fn(a, *extra, stream) -> status.  split: the caller forces a split of the reduction, which
+    cannot run without a workspace (-3, like a configuration the planner refuses)."""
+    ws = _attach_ws(a, floats_fn, device, spare, *extra)
+    if split and ws is None:
+        return -3
+    return run_fn(C.byref(a), *extra, current_stream())
 
 
 class _ConvFn(torch.autograd.Function):
@@ -278,67 +314,89 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        l = _lib.lib()
         x1, x2, weight, y = ctx.saved_tensors
         ksize, pad, act, slope, up1 = ctx.cfg
-        s = current_stream()
         dy = _c(dy)
-        B, cout, H, W = y.shape
-        C1 = x1.shape[1]
-        C2 = 0 if x2 is None else x2.shape[1]
         if ACT[act] != 0 and not ctx.grad_is_dz:
             dz = torch.empty_like(dy)
-            check(l.wmd_act_bwd(ptr(dy), ptr(y), ptr(dz), dy.numel(), ACT[act], float(slope), s), "wmd_act_bwd")
+            check(_lib.lib().wmd_act_bwd(ptr(dy), ptr(y), ptr(dz), dy.numel(), ACT[act], float(slope), current_stream()), "wmd_act_bwd")
         else:
             dz = dy     # no activation, or every consumer already multiplied its contribution by f'(y) (x1_gate on their side)
-        gate_act, gate_slope = (ACT[ctx.x1_gate[0]], float(ctx.x1_gate[1])) if ctx.x1_gate else (0, 0.0)
-        need_x1, need_x2, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and x2 is not None, ctx.needs_input_grad[2]
-        dx1 = dx2 = dw = db = None
-        if need_x1 or need_x2:
-            wpd = pack_weights(weight, dgrad=True)
-            wpdw = pack_weights_wino(weight, dgrad=True)   # kept alive in this scope for the launch
-            dx1 = torch.empty_like(x1) if need_x1 else None
-            dx2 = torch.empty_like(x2) if need_x2 else None
-            a = _lib.ConvDgradArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad],
-                                   dz=ptr(dz), wp_dgrad=ptr(wpd), dx1=ptr(dx1), dx2=ptr(dx2), workspace=None,
-                                   workspace_floats=0, tune_cfg=0, tune_ksplit=0, wp_dgrad_wino=ptr(wpdw),
-                                   x1_fwd=ptr(x1) if gate_act else None, x1_act=gate_act, x1_slope=gate_slope)
-            _dgrad_launch(a, dy.device, 9 if ksize == 3 else 1)
-        if need_w or (ctx.has_bias and ctx.needs_input_grad[3]):
-            dw = torch.empty_like(weight)
-            db = torch.empty(cout, device=dy.device, dtype=torch.float32) if ctx.has_bias else None
-            a = _lib.ConvWgradArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad],
-                                   x1=ptr(x1), x2=ptr(x2), dz=ptr(dz), dw=ptr(dw), dbias=ptr(db), workspace=None,
-                                   workspace_floats=0, tune_cfg=0, tune_nsplit=0)
-            _wgrad_launch(a, dy.device)
-        return dx1, dx2, dw, db, None, None, None, None, None, None, None
+        need = ctx.needs_input_grad
+        return _conv_backward_raw(x1, x2, weight, dz, ksize, pad, up1, ctx.has_bias, need[0], need[1] and x2 is not None,
+                                  need[2] or (ctx.has_bias and need[3]), ctx.x1_gate) + (None,) * 7
 
 
-_WGRAD_NAMES = None
+def _conv_backward_raw(x1, x2, weight, dz, ksize, pad, up1, has_bias, need_x1, need_x2, need_w, x1_gate=None):
+    """dgrad + wgrad through the C ABI for an already-differentiated pre-activation gradient dz -> (dx1, dx2, dw, db)."""
+    dz = _c(dz)
+    dx1 = dx2 = dw = db = None
+    if need_x1 or need_x2:
+        wpd, wpdw = pack_weights(weight, dgrad=True), pack_weights_wino(weight, dgrad=True)
+        dx1 = torch.empty_like(x1) if need_x1 else None
+        dx2 = torch.empty_like(x2) if need_x2 else None
+        _dgrad(dz, wpd, wpdw, x1, x2, dx1, dx2, ksize, pad, up1, x1_gate)
+    if need_w:
+        dw = torch.empty_like(weight)
+        db = torch.empty(dz.shape[1], device=dz.device, dtype=torch.float32) if has_bias else None
+        _wgrad(dz, x1, x2, dw, db, ksize, pad, up1)
+    return dx1, dx2, dw, db
 
 
-def _wgrad_launch(a, device):
-    """wmd_conv_wgrad with the kernel family / tile chosen per problem signature on the device (3x3: the Winograd
-    F(2x2,3x3) weight-gradient tiles against the direct kernel), like the forward and the data gradient."""
-    global _WGRAD_NAMES
+def _gate(x_gate):
+    """(activation name, slope) or None -> (activation code, slope) of the C ABI."""
+    return (ACT[x_gate[0]], float(x_gate[1])) if x_gate else (0, 0.0)
+
+
+@functools.lru_cache(None)
+def _config_names(family):
+    """The configuration table of a kernel family of the library ("wmd_conv_wgrad", "wmd_conv_bf16"), read once."""
     l = _lib.lib()
-    stream = current_stream()
-    keep = []
+    return [getattr(l, family + "_config_name")(i).decode() for i in range(getattr(l, family + "_num_configs")())]
+
+
+def _dgrad(dz, wpd, wpdw, x1, x2, dx1, dx2, ksize, pad, up1, x1_gate=None):
+    """wmd_conv_dgrad of dz [B,Cout,H,W] into dx1 / dx2 (either may be None) from the data-gradient weight images wpd (direct)
+    and wpdw (Winograd or None), the (tile, split-K) choice autotuned per problem signature like the forward.  x1_gate: x1 is
+    the output of that activation and dx1 comes back multiplied by its derivative."""
+    l = _lib.lib()
+    B, cout, H, W = dz.shape
+    gate_act, gate_slope = _gate(x1_gate)
+    a = _lib.ConvDgradArgs(B=B, H=H, W=W, C1=x1.shape[1], up1=up1, C2=0 if x2 is None else x2.shape[1], Cout=cout, ksize=ksize,
+                           pad_mode=PAD[pad], dz=ptr(dz), wp_dgrad=ptr(wpd), dx1=ptr(dx1), dx2=ptr(dx2), workspace=None,
+                           workspace_floats=0, tune_cfg=0, tune_ksplit=0, wp_dgrad_wino=ptr(wpdw),
+                           x1_fwd=ptr(x1) if gate_act else None, x1_act=gate_act, x1_slope=gate_slope)
+
+    def launch(cfg, ks):
+        a.tune_cfg, a.tune_ksplit = cfg, ks
+        return _launch_ws(a, l.wmd_conv_dgrad_workspace_floats, l.wmd_conv_dgrad, dz.device, True)
+
+    choice = (0, 0)
+    if tuner.enabled:
+        key = "dgrad|%d|%d|%d|%d|%d|%d|%d|%d|%d" % (a.B, a.H, a.W, a.C1, a.up1, a.C2, a.Cout, a.ksize, int(bool(a.dx1)) + 2 * int(bool(a.dx2)))
+        if a.ksize == 3 and not a.wp_dgrad_wino:
+            key += "|direct"
+        choice = tuner.pick(key, 9 if ksize == 3 else 1, launch)
+    check(launch(*choice), "wmd_conv_dgrad")
+
+
+def _wgrad(dz, x1, x2, dw, db, ksize, pad, up1):
+    """wmd_conv_wgrad of dz [B,Cout,H,W] against cat[up(x1), x2] into dw / db (db may be None), the kernel family / tile chosen
+    per problem signature on the device (3x3: the Winograd F(2x2,3x3) weight-gradient tiles against the direct kernel)."""
+    l = _lib.lib()
+    B, cout, H, W = dz.shape
+    a = _lib.ConvWgradArgs(B=B, H=H, W=W, C1=x1.shape[1], up1=up1, C2=0 if x2 is None else x2.shape[1], Cout=cout, ksize=ksize,
+                           pad_mode=PAD[pad], x1=ptr(x1), x2=ptr(x2), dz=ptr(dz), dw=ptr(dw), dbias=ptr(db), workspace=None,
+                           workspace_floats=0, tune_cfg=0, tune_nsplit=0)
 
     def launch(cfg):
         a.tune_cfg, a.tune_nsplit = cfg, 0
-        n = l.wmd_conv_wgrad_workspace_floats(C.byref(a))
-        ws = torch.empty(max(n, 1), device=device, dtype=torch.float32)
-        keep[:] = [ws]
-        a.workspace, a.workspace_floats = ptr(ws), n
-        return l.wmd_conv_wgrad(C.byref(a), stream)
+        return _launch_ws(a, l.wmd_conv_wgrad_workspace_floats, l.wmd_conv_wgrad, dz.device, True)
 
     cfg = 0
     if tuner.enabled and a.ksize == 3:
-        if _WGRAD_NAMES is None:
-            _WGRAD_NAMES = [l.wmd_conv_wgrad_config_name(i).decode() for i in range(l.wmd_conv_wgrad_num_configs())]
         key = "wgrad|%d|%d|%d|%d|%d|%d|%d|%d" % (a.B, a.H, a.W, a.C1, a.up1, a.C2, a.Cout, a.ksize)
-        cands = [("library", 0), ("direct", -1)] + [(n, i + 1) for i, n in enumerate(_WGRAD_NAMES)]
+        cands = [("library", 0), ("direct", -1)] + [(n, i + 1) for i, n in enumerate(_config_names("wmd_conv_wgrad"))]
         cfg = tuner.choose(key, cands, launch)
     check(launch(cfg), "wmd_conv_wgrad")
 
@@ -397,32 +455,22 @@ def conv2d_fused(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none
 
 PRECISION_TERMS = {"bf16x3": 3, "bf16": 1}   # trunk precision mode -> bf16 products per k-step ("fp32": the ordinary operators)
 _BF16_KSPLITS = (1, 2, 3, 4, 6, 8)
-_BF16_NAMES = None
 
 
 def pack_weights_bf16(weight, terms):
     """[Cout,Cin,3,3] -> bf16 fragment image of wmd_conv_bf16_pack_weights (terms = 3: head plane + tail plane); memoised on
-    the weight like pack_weights (own slot per `terms`, same tag, same invalidate_packs generation, no memo while capturing)."""
-    l = _lib.lib()
-    tag = (weight._version, weight.data_ptr(), weight.device, _pack_generation[0])
-    slot = "_wmd_pack_b%d" % terms
-    if _PACK_CACHE:
-        hit = getattr(weight, slot, None)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
-    cout, cin = weight.shape[:2]
-    n = l.wmd_conv_bf16_packed_weight_bytes(cout, cin, terms)
-    if n == 0 or tuple(weight.shape[2:]) != (3, 3):
-        raise _lib.WmdError("no bf16 weight image for a %s filter with terms=%r" % (tuple(weight.shape), terms))
-    wp = torch.empty(n, device=weight.device, dtype=torch.uint8)
-    check(l.wmd_conv_bf16_pack_weights(ptr(_c(weight.detach())), ptr(wp), cout, cin, terms, current_stream()),
-          "wmd_conv_bf16_pack_weights")
-    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
-        try:
-            setattr(weight, slot, (tag, wp))
-        except AttributeError:
-            pass
-    return wp
+    the weight like pack_weights (own slot per `terms`).  Raises for a filter or `terms` the library has no image for."""
+    def build():
+        l = _lib.lib()
+        cout, cin = weight.shape[:2]
+        n = l.wmd_conv_bf16_packed_weight_bytes(cout, cin, terms)
+        if n == 0 or tuple(weight.shape[2:]) != (3, 3):
+            raise _lib.WmdError("no bf16 weight image for a %s filter with terms=%r" % (tuple(weight.shape), terms))
+        wp = torch.empty(n, device=weight.device, dtype=torch.uint8)
+        check(l.wmd_conv_bf16_pack_weights(ptr(_c(weight.detach())), ptr(wp), cout, cin, terms, current_stream()),
+              "wmd_conv_bf16_pack_weights")
+        return (wp,)
+    return _memo(weight, "_wmd_pack_b%d" % terms, _pack_tag(weight), build)[0]
 
 
 def conv3x3_bf16_supported(B, H, W, C1, up1, C2, cout, pad="reflect", terms=3):
@@ -442,7 +490,6 @@ def conv3x3_bf16_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", ac
         raise _lib.WmdError("conv3x3_bf16_nograd is an inference operator (use conv2d_fused to train)")
     if terms not in (1, 3):
         raise _lib.WmdError("terms must be 1 or 3, got %r" % (terms,))
-    global _BF16_NAMES
     l = _lib.lib()
     x1, x2, bias = _c(x1), _c(x2), _c(bias)
     B, C1 = x1.shape[0], x1.shape[1]
@@ -461,27 +508,17 @@ def conv3x3_bf16_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", ac
     wp = pack_weights_bf16(weight, terms)
     y = torch.empty((B, cout, H, W), device=x1.device, dtype=torch.float32)
     a.wp, a.y = ptr(wp), ptr(y)
-    stream = current_stream()
-    keep = []
 
     def launch(choice):
         a.tune_cfg, a.tune_ksplit = choice
-        a.workspace, a.workspace_floats = None, 0
-        n = l.wmd_conv_bf16_workspace_floats(C.byref(a), terms)
-        if n:
-            ws = torch.empty(n, device=x1.device, dtype=torch.float32)
-            keep[:] = [ws]
-            a.workspace, a.workspace_floats = ptr(ws), n
-        return l.wmd_conv_bf16_fwd(C.byref(a), terms, stream)
+        return _launch_ws(a, l.wmd_conv_bf16_workspace_floats, l.wmd_conv_bf16_fwd, x1.device, False, terms)
 
     choice = (0, 0)
     if tuner.enabled:
-        if _BF16_NAMES is None:
-            _BF16_NAMES = [l.wmd_conv_bf16_config_name(i).decode() for i in range(l.wmd_conv_bf16_num_configs())]
         # keys of their own: no entry of a cache written for the fp32 operators is read or changed by this path
         key = "conv16|%d|%d|%d|%d|%d|%d|%d|%d" % (B, H, W, C1, up1, C2, cout, terms)
         nchunks = (C1 + C2) // 16
-        cands = [("library", (0, 0))] + [("%s|%d" % (n, ks), (i + 1, ks)) for i, n in enumerate(_BF16_NAMES)
+        cands = [("library", (0, 0))] + [("%s|%d" % (n, ks), (i + 1, ks)) for i, n in enumerate(_config_names("wmd_conv_bf16"))
                                          for ks in _BF16_KSPLITS if ks <= max(1, nchunks // 2)]
         choice = tuner.choose(key, cands, launch)
     check(launch(choice), "wmd_conv_bf16_fwd")
@@ -514,7 +551,7 @@ class _DwConvFn(torch.autograd.Function):
         dx2 = torch.empty_like(x2) if (x2 is not None and ctx.needs_input_grad[1]) else None
         dw = torch.empty_like(w) if ctx.needs_input_grad[2] else None
         n = l.wmd_dwconv3x3_bwd_workspace_floats(C.byref(a))
-        ws = torch.empty(max(n, 1), device=y.device, dtype=torch.float32)
+        ws = _workspace(n, y.device, True)
         check(l.wmd_dwconv3x3_bwd(C.byref(a), ptr(y), ptr(_c(dy)), ptr(dx1), ptr(dx2), ptr(dw), ptr(ws), n, current_stream()),
               "wmd_dwconv3x3_bwd")
         return dx1, dx2, dw, None, None
@@ -549,11 +586,7 @@ def _head_raw(xp, wp_, bp, xn, wn, bn, pad, mode, scale, save_sig):
 
 
 def _head_launch(l, a, device):
-    n = l.wmd_head3x3_workspace_floats(C.byref(a))
-    if n:
-        ws = torch.empty(n, device=device, dtype=torch.float32)
-        a.workspace, a.workspace_floats = ptr(ws), n
-    check(l.wmd_head3x3_fwd(C.byref(a), current_stream()), "wmd_head3x3_fwd")
+    check(_launch_ws(a, l.wmd_head3x3_workspace_floats, l.wmd_head3x3_fwd, device, False), "wmd_head3x3_fwd")
 
 
 class _HeadFn(torch.autograd.Function):
@@ -584,67 +617,9 @@ class _HeadFn(torch.autograd.Function):
                 dz = dy * (sign * scale)
             else:
                 dz = dy * sig * (1.0 - sig) * (sign * scale)
-            dx, dw, db = _conv_backward_raw(x, None, w, dz, 3, pad, 1, has_b,
-                                            ctx.needs_input_grad[base], True, x1_gate=ctx.x_gate)
+            dx, _, dw, db = _conv_backward_raw(x, None, w, dz, 3, pad, 1, has_b, ctx.needs_input_grad[base], False, True, ctx.x_gate)
             outs[base], outs[base + 1], outs[base + 2] = dx, dw, db
         return tuple(outs)
-
-
-def _dgrad_launch(a, device, taps):
-    """wmd_conv_dgrad with the (tile, split-K) choice autotuned per problem signature, like the forward."""
-    l = _lib.lib()
-    stream = current_stream()
-    keep = []
-
-    def launch(cfg, ks):
-        a.tune_cfg, a.tune_ksplit = cfg, ks
-        n = l.wmd_conv_dgrad_workspace_floats(C.byref(a))
-        ws = torch.empty(max(n, 1), device=device, dtype=torch.float32)
-        keep[:] = [ws]
-        a.workspace, a.workspace_floats = ptr(ws), n
-        return l.wmd_conv_dgrad(C.byref(a), stream)
-
-    choice = (0, 0)
-    if tuner.enabled:
-        key = "dgrad|%d|%d|%d|%d|%d|%d|%d|%d|%d" % (a.B, a.H, a.W, a.C1, a.up1, a.C2, a.Cout, a.ksize, int(bool(a.dx1)) + 2 * int(bool(a.dx2)))
-        if a.ksize == 3 and not a.wp_dgrad_wino:
-            key += "|direct"
-        choice = tuner.lookup(key)
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                choice = (0, 0)
-            else:
-                choice = tuner.tune(key, taps, launch)
-    check(launch(*choice), "wmd_conv_dgrad")
-
-
-def _conv_backward_raw(x1, x2, weight, dz, ksize, pad, up1, has_bias, need_x, need_w, x1_gate=None):
-    """dgrad + wgrad through the C ABI for an already-differentiated pre-activation gradient dz."""
-    l = _lib.lib()
-    s = current_stream()
-    B, cout, H, W = dz.shape
-    C1 = x1.shape[1]
-    C2 = 0 if x2 is None else x2.shape[1]
-    dz = _c(dz)
-    dx1 = dw = db = None
-    if need_x:
-        wpd = pack_weights(weight, dgrad=True)
-        wpdw = pack_weights_wino(weight, dgrad=True)
-        dx1 = torch.empty_like(x1)
-        gate_act, gate_slope = (ACT[x1_gate[0]], float(x1_gate[1])) if x1_gate else (0, 0.0)
-        a = _lib.ConvDgradArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad],
-                               dz=ptr(dz), wp_dgrad=ptr(wpd), dx1=ptr(dx1), dx2=None, workspace=None, workspace_floats=0,
-                               tune_cfg=0, tune_ksplit=0, wp_dgrad_wino=ptr(wpdw),
-                               x1_fwd=ptr(x1) if gate_act else None, x1_act=gate_act, x1_slope=gate_slope)
-        _dgrad_launch(a, dz.device, 9 if ksize == 3 else 1)
-    if need_w:
-        dw = torch.empty_like(weight)
-        db = torch.empty(cout, device=dz.device, dtype=torch.float32) if has_bias else None
-        a = _lib.ConvWgradArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad],
-                               x1=ptr(x1), x2=ptr(x2), dz=ptr(dz), dw=ptr(dw), dbias=ptr(db), workspace=None,
-                               workspace_floats=0, tune_cfg=0, tune_nsplit=0)
-        _wgrad_launch(a, dz.device)
-    return dx1, dw, db
 
 
 def head3x3(xp, weight_p, bias_p, xn=None, weight_n=None, bias_n=None, pad="reflect", mode=0, scale=1.0, x_gate=None):
@@ -652,6 +627,21 @@ def head3x3(xp, weight_p, bias_p, xn=None, weight_n=None, bias_n=None, pad="refl
     back multiplied by its derivative)."""
     _require_gpu(xp, weight_p, bias_p, xn, weight_n, bias_n)
     return _HeadFn.apply(xp, weight_p, bias_p, xn, weight_n, bias_n, pad, mode, scale, x_gate)
+
+
+def _heads_layout(params):
+    """(w1, b1, w3, b3) of the + head, the - head and optionally the LL head, flat -> heads [+, -, (LL)], has_ll, order (the
+    heads in the channel order of `mid` and of the stacked gradients: [LL, +, -]), offs {head: first channel of its 1x1
+    outputs in mid}, rows {head: first row of its 3x3 outputs in the stacked pre-sigmoid gradient}."""
+    heads = [params[i:i + 4] for i in range(0, len(params), 4)]
+    has_ll = len(heads) == 3
+    order = ([2] if has_ll else []) + [0, 1]
+    offs, rows, o, r = {}, {}, 0, 0
+    for k in order:
+        offs[k], rows[k] = o, r
+        o += heads[k][0].shape[0]
+        r += heads[k][2].shape[0]
+    return heads, has_ll, order, offs, rows
 
 
 class _StackedHeadsFn(torch.autograd.Function):
@@ -673,15 +663,9 @@ class _StackedHeadsFn(torch.autograd.Function):
     def forward(ctx, x, x_gate, scale_hf, scale_ll, *params):
         l = _lib.lib()
         x = _c(x)
-        heads = [params[i:i + 4] for i in range(0, len(params), 4)]       # [+, -, (LL)]
-        has_ll = len(heads) == 3
-        order = ([2] if has_ll else []) + [0, 1]                            # stacked channel order: [LL, +, -]
+        heads, has_ll, order, offs, _rows = _heads_layout(params)
         w1s, b1s = [heads[k][0] for k in order], [heads[k][1] for k in order]
         mid = conv1x1_stacked_nograd(x, w1s, b1s, act="leaky", slope=0.1)
-        offs, o = {}, 0
-        for k in order:
-            offs[k] = o
-            o += heads[k][0].shape[0]
         B, Ct, H, W = mid.shape
         plane = H * W
         base = mid.data_ptr()
@@ -706,7 +690,7 @@ class _StackedHeadsFn(torch.autograd.Function):
         if has_ll:
             yl, sl, _ = run(1, scale_ll, 2)
         ctx.save_for_backward(x, mid, sp, sn, sl, *params)
-        ctx.meta = (x_gate, float(scale_hf), float(scale_ll), has_ll, order, offs)
+        ctx.meta = (x_gate, float(scale_hf), float(scale_ll))
         ctx.mark_non_differentiable(mid)
         return (yh, yl if has_ll else yh.new_empty(0), mid)
 
@@ -717,131 +701,119 @@ class _StackedHeadsFn(torch.autograd.Function):
         return (dx, None, None, None) + tuple(grads)
 
 
+def _heads_bwd_3x3(own, heads, order, offs, rows, dy3, mid, w1s):
+    """3x3 stage of _stacked_heads_backward, on its own kernels (`own`) or on the generic ones: -> ({head: (dw3, db3)}, dzmid =
+    the gradient of `mid` gated by LeakyReLU'(mid), pending, wpd1).  pending: (Head3x3BwdArgs, the tensors it points to) of
+    the own-kernel stage, which the 1x1 stage launches (alone or merged with itself); None when the stage has been launched.
+    wpd1: the data-gradient image of the stacked 1x1 filter w1s (None: not wanted) -- the generic route packs it in the same
+    launch as its own images; otherwise None."""
+    l = _lib.lib()
+    B, Ct, H, W = mid.shape
+    n_out, dev = dy3.shape[1], mid.device
+    dzmid = torch.empty_like(mid)
+    if own:
+        # wmd_head_bwd.hip: tap-partial rows gathered from dy3, one pass over mid each for the data gradient and for the weight
+        # + bias gradients of every head
+        dw3s = {k: torch.empty_like(heads[k][2]) for k in order}
+        db3s = {k: torch.empty(heads[k][2].shape[0], device=dev, dtype=torch.float32) for k in order}
+        a = _lib.Head3x3BwdArgs(B=B, H=H, W=W, Ct=Ct, n_out=n_out, pad_mode=PAD["reflect"], act=ACT["leaky"], slope=0.1,
+                                dy3=ptr(dy3), mid=ptr(mid), dzmid=ptr(dzmid), n_heads=len(order), workspace=None,
+                                workspace_floats=0)
+        keep = []
+        for i, k in enumerate(order):
+            w3c = _c(heads[k][2].detach())
+            keep.append(w3c)
+            a.head[i] = _lib.HeadBwdHead(row0=rows[k], nrows=w3c.shape[0], ch0=offs[k], nch=w3c.shape[1], w3=ptr(w3c),
+                                         dw3=ptr(dw3s[k]), db3=ptr(db3s[k]))
+        keep.append(_attach_ws(a, l.wmd_head3x3_bwd_workspace_floats, dev, True))
+        return {k: (dw3s[k], db3s[k]) for k in order}, dzmid, (a, keep), None
+    # the heads as ONE convolution with a block-diagonal filter [n_out, Ct, 3, 3]
+    w3bd = torch.zeros((n_out, Ct, 3, 3), device=dev, dtype=torch.float32)
+    blocks = {k: (slice(rows[k], rows[k] + heads[k][2].shape[0]), slice(offs[k], offs[k] + heads[k][2].shape[1])) for k in order}
+    for k in order:
+        w3bd[blocks[k]] = heads[k][2].detach()
+    # its weight gradient (the diagonal blocks are the heads' gradients) ...
+    dw3f = torch.empty_like(w3bd)
+    db3f = torch.empty(n_out, device=dev, dtype=torch.float32)
+    _wgrad(dy3, mid, None, dw3f, db3f, 3, "reflect", 1)
+    # ... and data gradient; the three weight images of this backward (3x3 data gradient direct + Winograd, 1x1 data gradient)
+    # come from one launch
+    imgs = pack_many([(w3bd, ("dgrad", "wino_dgrad") if _WINOGRAD else ("dgrad",))] + ([(w1s, ("dgrad",))] if w1s is not None else []))
+    _dgrad(dy3, imgs[0]["dgrad"], imgs[0].get("wino_dgrad"), mid, None, dzmid, None, 3, "reflect", 1, ("leaky", 0.1))
+    return ({k: (dw3f[blocks[k]], db3f[blocks[k][0]]) for k in order}, dzmid, None,
+            imgs[1]["dgrad"] if w1s is not None else None)
+
+
+def _heads_bwd_1x1(own, merged, pending, x, w1s, dzmid, x_gate, want_dx, wpd1):
+    """1x1 stage of _stacked_heads_backward, after (or, `merged`, in the launches of) the pending 3x3 stage: -> (dx or None, the
+    stacked dw1 [Ct,C,1,1], db1 [Ct]).  dx is gated by the caller's activation x_gate if x has one."""
+    l = _lib.lib()
+    B, C_in, H, W = x.shape
+    Ct, dev = w1s.shape[0], x.device
+    dw1f = torch.empty_like(w1s)
+    db1f = torch.empty(Ct, device=dev, dtype=torch.float32)
+    dx = torch.empty_like(x) if want_dx else None
+
+    def launch_pending():
+        if pending is not None:
+            check(l.wmd_head3x3_bwd(C.byref(pending[0]), current_stream()), "wmd_head3x3_bwd")
+
+    if own:
+        # wmd_head_bwd1.hip: one pass over dz and x each for dx and for the stacked weight + bias gradient
+        gate_act, gate_slope = _gate(x_gate)
+        w1c = _c(w1s.reshape(Ct, C_in))
+        a = _lib.Head1x1BwdArgs(B=B, H=H, W=W, C=C_in, Ct=Ct, x_act=gate_act, x_slope=gate_slope, dz=ptr(dzmid), x=ptr(x),
+                                w1=ptr(w1c), dx=ptr(dx), dw1=ptr(dw1f), db1=ptr(db1f), workspace=None, workspace_floats=0)
+        ws1 = _attach_ws(a, l.wmd_head1x1_bwd_workspace_floats, dev, True)
+        if merged:
+            # three launches for both stages: 3x3 data gradient, then [3x3 weights | 1x1 data | 1x1 weights] as one, then
+            # both reduces as one
+            check(l.wmd_head_bwd(C.byref(pending[0]), C.byref(a), current_stream()), "wmd_head_bwd")
+        else:
+            launch_pending()
+            check(l.wmd_head1x1_bwd(C.byref(a), current_stream()), "wmd_head1x1_bwd")
+    else:
+        launch_pending()
+        # weight gradient of the stacked filter and data gradient (one GEMM over all heads' mid channels)
+        _wgrad(dzmid, x, None, dw1f, db1f, 1, "zero", 1)
+        if want_dx:
+            if wpd1 is None:
+                wpd1 = pack_many([(w1s, ("dgrad",))])[0]["dgrad"]
+            _dgrad(dzmid, wpd1, None, x, None, dx, None, 1, "zero", 1, x_gate)
+    return dx, dw1f, db1f
+
+
 def _stacked_heads_backward(x, mid, sp, sn, sl, params, meta, d_yh, d_yl, want_dx):
     """Backward of a level's stacked heads from the saved 1x1 outputs `mid` and sigmoid outputs sp / sn / sl (see
     _StackedHeadsFn): -> (dx, [dw1, db1, dw3, db3 of the + head, the - head(, the LL head)])."""
-    if True:
-        l = _lib.lib()
-        x_gate, s_hf, s_ll, has_ll, order, offs = meta
-        heads = [params[i:i + 4] for i in range(0, len(params), 4)]
-        B, Ct, H, W = mid.shape
-        C_in = x.shape[1]
-        dev = x.device
-        # pre-sigmoid gradients of every head, stacked in the channel order of `mid`: [LL (1)], + (3), - (3)
-        parts = []
-        if has_ll:
-            parts.append(torch.zeros_like(sl) if d_yl is None or d_yl.numel() == 0 else _c(d_yl) * sl * (1.0 - sl) * s_ll)
-        d_yh = torch.zeros_like(sp) if d_yh is None else _c(d_yh)      # yh unused by the loss
-        parts.append(d_yh * sp * (1.0 - sp) * s_hf)
-        parts.append(d_yh * sn * (1.0 - sn) * (-s_hf))
-        dy3 = torch.cat(parts, 1)
-        n_out = dy3.shape[1]
-        rows, r = {}, 0
-        for k in order:
-            rows[k] = r
-            r += heads[k][2].shape[0]
-        w1s = torch.cat([heads[k][0].detach() for k in order], 0)
-        dzmid = torch.empty_like(mid)
-        a3_pending = None
-        nsl = sum((heads[k][2].shape[1] + 63) // 64 for k in order)
-        # (worth it where a level has pixels to spread: >= 256 wave tiles; the coarsest level stays on the generic kernels, which
-        # split its few pixels over channels instead -- tools/head_bwd_microbench.py)
-        if _HEAD_BWD and nsl <= 24 and B * H * W >= _HEAD_BWD_MIN_PIXELS and all(heads[k][2].shape[0] in (1, 3) for k in order):
-            # the 3x3 stage on its own kernels (wmd_head_bwd.hip): tap-partial rows gathered from dy3, one pass over mid each for
-            # the data gradient (returned gated by LeakyReLU'(mid)) and for the weight + bias gradients of every head
-            dw3s = {k: torch.empty_like(heads[k][2]) for k in order}
-            db3s = {k: torch.empty(heads[k][2].shape[0], device=dev, dtype=torch.float32) for k in order}
-            a = _lib.Head3x3BwdArgs(B=B, H=H, W=W, Ct=Ct, n_out=n_out, pad_mode=PAD["reflect"], act=ACT["leaky"], slope=0.1,
-                                    dy3=ptr(dy3), mid=ptr(mid), dzmid=ptr(dzmid), n_heads=len(order), workspace=None,
-                                    workspace_floats=0)
-            keep = []
-            for i, k in enumerate(order):
-                w3c = _c(heads[k][2].detach())
-                keep.append(w3c)
-                a.head[i] = _lib.HeadBwdHead(row0=rows[k], nrows=w3c.shape[0], ch0=offs[k], nch=w3c.shape[1], w3=ptr(w3c),
-                                             dw3=ptr(dw3s[k]), db3=ptr(db3s[k]))
-            n = l.wmd_head3x3_bwd_workspace_floats(C.byref(a))
-            ws = torch.empty(max(n, 1), device=dev, dtype=torch.float32)
-            a.workspace, a.workspace_floats = ptr(ws), n
-            a3_pending = a        # launched below: alone, or merged with the 1x1 stage (wmd_head_bwd)
-            wpd1 = None        # packed by the generic 1x1 path on demand
-            head_grads3 = lambda k: (dw3s[k], db3s[k])
-        else:
-            # block-diagonal 3x3 filter [n_out, Ct, 3, 3]
-            w3bd = torch.zeros((n_out, Ct, 3, 3), device=dev, dtype=torch.float32)
-            for k in order:
-                w3 = heads[k][2].detach()
-                w3bd[rows[k]:rows[k] + w3.shape[0], offs[k]:offs[k] + w3.shape[1]] = w3
-            # 3x3: weight gradient of the stacked filter (diagonal blocks are the heads' gradients) ...
-            dw3f = torch.empty_like(w3bd)
-            db3f = torch.empty(n_out, device=dev, dtype=torch.float32)
-            a = _lib.ConvWgradArgs(B=B, H=H, W=W, C1=Ct, up1=1, C2=0, Cout=n_out, ksize=3, pad_mode=PAD["reflect"], x1=ptr(mid), x2=None,
-                                   dz=ptr(dy3), dw=ptr(dw3f), dbias=ptr(db3f), workspace=None, workspace_floats=0, tune_cfg=0,
-                                   tune_nsplit=0)
-            _wgrad_launch(a, dev)
-            # ... and data gradient, gated by LeakyReLU'(mid): dzmid
-            # the three weight images of this backward (3x3 data gradient direct + Winograd, 1x1 data gradient) in one launch
-            imgs = pack_many([(w3bd, ("dgrad", "wino_dgrad") if _WINOGRAD else ("dgrad",))] + ([(w1s, ("dgrad",))] if want_dx else []))
-            wpd, wpdw = imgs[0]["dgrad"], imgs[0].get("wino_dgrad")
-            a = _lib.ConvDgradArgs(B=B, H=H, W=W, C1=Ct, up1=1, C2=0, Cout=n_out, ksize=3, pad_mode=PAD["reflect"], dz=ptr(dy3),
-                                   wp_dgrad=ptr(wpd), dx1=ptr(dzmid), dx2=None, workspace=None, workspace_floats=0, tune_cfg=0,
-                                   tune_ksplit=0, wp_dgrad_wino=ptr(wpdw), x1_fwd=ptr(mid), x1_act=ACT["leaky"], x1_slope=0.1)
-            _dgrad_launch(a, dev, 9)
-            wpd1 = imgs[1]["dgrad"] if want_dx else None
-            head_grads3 = lambda k: (dw3f[rows[k]:rows[k] + heads[k][2].shape[0], offs[k]:offs[k] + heads[k][2].shape[1]].contiguous(),
-                                     db3f[rows[k]:rows[k] + heads[k][2].shape[0]])
-        dw1f = torch.empty_like(w1s)
-        db1f = torch.empty(Ct, device=dev, dtype=torch.float32)
-        dx = torch.empty_like(x) if want_dx else None
-        gate_act, gate_slope = (ACT[x_gate[0]], float(x_gate[1])) if x_gate else (0, 0.0)
-        # (alone they only win at the finest level; as components of the merged second-stage launch -- a level without the
-        # low-pass head whose 3x3 stage runs on its own kernels too -- wherever those do)
-        merged = a3_pending is not None and not has_ll and _HEAD_BWD_MERGED
-        if _HEAD_BWD and B * H * W >= (_HEAD_BWD_MIN_PIXELS if merged else _HEAD_BWD1_MIN_PIXELS) and Ct % 8 == 0 and \
-                gate_act in (ACT["none"], ACT["leaky"], ACT["elu"]):
-            # 1x1 stage on its own kernels (wmd_head_bwd1.hip): one pass over dz and x each for dx (gated by the caller's
-            # activation if x has one) and for the stacked weight + bias gradient
-            w1c = _c(w1s.reshape(Ct, C_in))
-            a = _lib.Head1x1BwdArgs(B=B, H=H, W=W, C=C_in, Ct=Ct, x_act=gate_act, x_slope=gate_slope, dz=ptr(dzmid), x=ptr(x),
-                                    w1=ptr(w1c), dx=ptr(dx), dw1=ptr(dw1f), db1=ptr(db1f), workspace=None, workspace_floats=0)
-            n = l.wmd_head1x1_bwd_workspace_floats(C.byref(a))
-            ws1 = torch.empty(max(n, 1), device=dev, dtype=torch.float32)
-            a.workspace, a.workspace_floats = ptr(ws1), n
-            if merged:
-                # three launches for both stages: 3x3 data gradient, then [3x3 weights | 1x1 data | 1x1 weights] as one, then
-                # both reduces as one
-                check(l.wmd_head_bwd(C.byref(a3_pending), C.byref(a), current_stream()), "wmd_head_bwd")
-                a3_pending = None
-            else:
-                if a3_pending is not None:
-                    check(l.wmd_head3x3_bwd(C.byref(a3_pending), current_stream()), "wmd_head3x3_bwd")
-                    a3_pending = None
-                check(l.wmd_head1x1_bwd(C.byref(a), current_stream()), "wmd_head1x1_bwd")
-        else:
-            if a3_pending is not None:
-                check(l.wmd_head3x3_bwd(C.byref(a3_pending), current_stream()), "wmd_head3x3_bwd")
-                a3_pending = None
-            # 1x1: weight gradient of the stacked filter ...
-            a = _lib.ConvWgradArgs(B=B, H=H, W=W, C1=C_in, up1=1, C2=0, Cout=Ct, ksize=1, pad_mode=PAD["zero"], x1=ptr(x), x2=None,
-                                   dz=ptr(dzmid), dw=ptr(dw1f), dbias=ptr(db1f), workspace=None, workspace_floats=0, tune_cfg=0,
-                                   tune_nsplit=0)
-            _wgrad_launch(a, dev)
-            # ... and data gradient (one GEMM over all heads' mid channels), gated by the caller's activation if x has one
-            if want_dx:
-                if wpd1 is None:
-                    wpd1 = pack_many([(w1s, ("dgrad",))])[0]["dgrad"]
-                a = _lib.ConvDgradArgs(B=B, H=H, W=W, C1=C_in, up1=1, C2=0, Cout=Ct, ksize=1, pad_mode=PAD["zero"], dz=ptr(dzmid),
-                                       wp_dgrad=ptr(wpd1), dx1=ptr(dx), dx2=None, workspace=None, workspace_floats=0, tune_cfg=0,
-                                       tune_ksplit=0, wp_dgrad_wino=None, x1_fwd=ptr(x) if gate_act else None, x1_act=gate_act,
-                                       x1_slope=gate_slope)
-                _dgrad_launch(a, dev, 1)
-        grads = []
-        for k in range(len(heads)):
-            w1, _b1, w3, _b3 = heads[k]
-            c1, c3 = w1.shape[0], w3.shape[0]
-            dw3k, db3k = head_grads3(k)
-            grads += [dw1f[offs[k]:offs[k] + c1].reshape(w1.shape), db1f[offs[k]:offs[k] + c1], dw3k, db3k]
-        return dx, grads
+    x_gate, s_hf, s_ll = meta
+    heads, has_ll, order, offs, rows = _heads_layout(params)
+    B, Ct, H, W = mid.shape
+    # pre-sigmoid gradients of every head, stacked in the channel order of `mid`: [LL (1)], + (3), - (3)
+    parts = []
+    if has_ll:
+        parts.append(torch.zeros_like(sl) if d_yl is None or d_yl.numel() == 0 else _c(d_yl) * sl * (1.0 - sl) * s_ll)
+    d_yh = torch.zeros_like(sp) if d_yh is None else _c(d_yh)      # yh unused by the loss
+    parts.append(d_yh * sp * (1.0 - sp) * s_hf)
+    parts.append(d_yh * sn * (1.0 - sn) * (-s_hf))
+    dy3 = torch.cat(parts, 1)
+    w1s = torch.cat([heads[k][0].detach() for k in order], 0)
+    nsl = sum((heads[k][2].shape[1] + 63) // 64 for k in order)
+    # (worth it where a level has pixels to spread: >= 256 wave tiles; the coarsest level stays on the generic kernels, which
+    # split its few pixels over channels instead -- tools/head_bwd_microbench.py)
+    own3 = _HEAD_BWD and nsl <= 24 and B * H * W >= _HEAD_BWD_MIN_PIXELS and all(heads[k][2].shape[0] in (1, 3) for k in order)
+    grads3, dzmid, pending, wpd1 = _heads_bwd_3x3(own3, heads, order, offs, rows, dy3, mid, w1s if want_dx else None)
+    # (alone the 1x1 kernels only win at the finest level; as components of the merged second-stage launch -- a level without
+    # the low-pass head whose 3x3 stage runs on its own kernels too -- wherever those do)
+    merged = pending is not None and not has_ll and _HEAD_BWD_MERGED
+    own1 = _HEAD_BWD and B * H * W >= (_HEAD_BWD_MIN_PIXELS if merged else _HEAD_BWD1_MIN_PIXELS) and Ct % 8 == 0 and \
+        _gate(x_gate)[0] in (ACT["none"], ACT["leaky"], ACT["elu"])
+    dx, dw1f, db1f = _heads_bwd_1x1(own1, merged, pending, x, w1s, dzmid, x_gate, want_dx, wpd1)
+    grads = []
+    for k, (w1, _b1, _w3, _b3) in enumerate(heads):
+        c1 = w1.shape[0]
+        grads += [dw1f[offs[k]:offs[k] + c1].reshape(w1.shape), db1f[offs[k]:offs[k] + c1], grads3[k][0].contiguous(), grads3[k][1]]
+    return dx, grads
 
 
 def stacked_heads(x, head_p, head_n, scale_hf, head_ll=None, scale_ll=1.0, x_gate=None, return_mid=False):
@@ -861,31 +833,21 @@ def stacked_heads(x, head_p, head_n, scale_hf, head_ll=None, scale_ll=1.0, x_gat
 
 def stacked_pack(weights, biases):
     """Packed image + bias of several [Cout_k, Cin, 1, 1] filters stacked along Cout (memoised on weights[0])."""
-    couts = [w.shape[0] for w in weights]
-    if any(c % 16 for c in couts[:-1]):
+    if any(w.shape[0] % 16 for w in weights[:-1]):
         raise _lib.WmdError("stacked heads need out-channel counts that are multiples of 16")
-    tag = tuple((w._version, w.data_ptr(), b._version, b.data_ptr()) for w, b in zip(weights, biases)) + (_pack_generation[0],)
-    hit = getattr(weights[0], "_wmd_pack_stack", None) if _PACK_CACHE else None
-    if hit is not None and hit[0] == tag:
-        return hit[1], hit[2]
-    _imgs, wp = pack_many([(w, ("fwd",)) for w in weights], with_buffer=True)   # consecutive slices = the stacked image
-    bias = torch.cat([b.detach() for b in biases])
-    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
-        try:
-            weights[0]._wmd_pack_stack = (tag, wp, bias)
-        except AttributeError:
-            pass
-    return wp, bias
+
+    def build():
+        _imgs, wp = pack_many([(w, ("fwd",)) for w in weights], with_buffer=True)   # consecutive slices = the stacked image
+        return wp, torch.cat([b.detach() for b in biases])
+    return _memo(weights[0], "_wmd_pack_stack", _pack_tag(*[t for wb in zip(weights, biases) for t in wb]), build)
 
 
 def conv1x1_stacked_nograd(x, weights, biases, act="leaky", slope=0.1):
     """Several 1x1 convolutions of the SAME input as one launch: their packed weight images are simply
     concatenated along the out-channel-tile axis (every Cout is a multiple of 16), so x is read once.
     Returns [B, sum(Cout_k), H, W]."""
-    x = _c(x)
-    couts = [w.shape[0] for w in weights]
     wp, bias = stacked_pack(weights, biases)
-    return _conv_fwd_raw(x, None, wp, bias, sum(couts), 1, "zero", act, slope, 1)
+    return _conv_fwd_raw(_c(x), None, wp, bias, sum(w.shape[0] for w in weights), 1, "zero", act, slope, 1)
 
 
 def head3x3_nograd(x_full, cin, off_p, weight_p, bias_p, off_n=None, weight_n=None, bias_n=None, pad="reflect", mode=0,
@@ -908,47 +870,26 @@ def head3x3_nograd(x_full, cin, off_p, weight_p, bias_p, off_n=None, weight_n=No
 
 def _tap_partial_pack(w3p, w3n):
     """[3,C,3,3] x 2 -> two packed [27,C,1,1] images (row co*9+tap), memoised on w3p."""
-    tag = (w3p._version, w3p.data_ptr(), w3n._version, w3n.data_ptr(), _pack_generation[0])
-    hit = getattr(w3p, "_wmd_pack_t27", None) if _PACK_CACHE else None
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    cin = w3p.shape[1]
-    w27s = [w.detach().permute(0, 2, 3, 1).reshape(27, cin, 1, 1).contiguous() for w in (w3p, w3n)]
-    _imgs, wp = pack_many([(w, ("fwd",)) for w in w27s], with_buffer=True)
-    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
-        try:
-            w3p._wmd_pack_t27 = (tag, wp)
-        except AttributeError:
-            pass
-    return wp
+    def build():
+        cin = w3p.shape[1]
+        w27s = [w.detach().permute(0, 2, 3, 1).reshape(27, cin, 1, 1).contiguous() for w in (w3p, w3n)]
+        return (pack_many([(w, ("fwd",)) for w in w27s], with_buffer=True)[1],)
+    return _memo(w3p, "_wmd_pack_t27", _pack_tag(w3p, w3n), build)[0]
 
 
 def _ll_chain_pack(w1l, w3l):
     """Weight images of the low-pass chain for wmd_head_fused_fwd(chain = 1): the [C/4,C,1,1] filter as it is, and the
     [1,C/4,3,3] filter as a [27,C/4,1,1] image whose rows 0..8 are its nine taps (rows 9..26 zero).  Memoised on w1l."""
-    tag = (w1l._version, w1l.data_ptr(), w3l._version, w3l.data_ptr(), _pack_generation[0])
-    hit = getattr(w1l, "_wmd_pack_ll", None) if _PACK_CACHE else None
-    if hit is not None and hit[0] == tag:
-        return hit[1], hit[2]
-    cm = w3l.shape[1]
-    w27 = torch.zeros((27, cm, 1, 1), device=w3l.device, dtype=torch.float32)
-    w27[:9, :, 0, 0] = w3l.detach()[0].permute(1, 2, 0).reshape(9, cm)
-    imgs = pack_many([(w1l, ("fwd",)), (w27, ("fwd",))])
-    wp1, wp2 = imgs[0]["fwd"], imgs[1]["fwd"]
-    if _PACK_CACHE and not torch.cuda.is_current_stream_capturing():
-        try:
-            w1l._wmd_pack_ll = (tag, wp1, wp2)
-        except AttributeError:
-            pass
-    return wp1, wp2
+    def build():
+        cm = w3l.shape[1]
+        w27 = torch.zeros((27, cm, 1, 1), device=w3l.device, dtype=torch.float32)
+        w27[:9, :, 0, 0] = w3l.detach()[0].permute(1, 2, 0).reshape(9, cm)
+        imgs = pack_many([(w1l, ("fwd",)), (w27, ("fwd",))])
+        return imgs[0]["fwd"], imgs[1]["fwd"]
+    return _memo(w1l, "_wmd_pack_ll", _pack_tag(w1l, w3l), build)
 
 
 FUSED_HEAD_WIDTHS = (32, 64, 128, 256)
-_HEAD_BWD = os.environ.get("WMD_HEAD_BWD", "1") != "0"                 # 0: 3x3 head backward on the generic dgrad / wgrad kernels
-_HEAD_BWD_MERGED = os.environ.get("WMD_HEAD_BWD_MERGED", "1") != "0"   # 0: wmd_head3x3_bwd + wmd_head1x1_bwd as separate launch sets
-_HEAD_BWD_MIN_PIXELS = int(os.environ.get("WMD_HEAD_BWD_MIN_PIXELS", "16384"))
-_HEAD_BWD1_MIN_PIXELS = int(os.environ.get("WMD_HEAD_BWD1_MIN_PIXELS", "196608"))     # same for the 1x1 stage (wmd_head1x1_bwd):
-# its kernels walk the whole channel sum per 64-pixel wave tile and only win where a level has thousands of tiles (the finest one)
 
 
 def head_level_folds_range_keys(C_):
@@ -1090,13 +1031,6 @@ def head_fused_level_nograd(x, head_p, head_n, scale, yl=None, disp_scale=None, 
     return yh.unsqueeze(1), out, disp
 
 
-_SHIFTSUM_CHAIN = os.environ.get("WMD_SHIFTSUM_CHAIN", "1") != "0"   # 0: one wmd_head_shiftsum_fwd launch per level
-# ... up to this many pixels at the finest chained level: the single launch removes two graph nodes from a latency-bound forward (one
-# frame 640x192: 0.221 -> 0.211 ms) but completes levels 4 and 3 from planes that have left the caches by then -- at batch 12
-# (92 160 pixels) the step measured 0.5 - 1 % slower with it (0.588 / 0.592 vs 0.585 / 0.584 ms medians, same box)
-_SHIFTSUM_CHAIN_MAX_PIXELS = int(os.environ.get("WMD_SHIFTSUM_CHAIN_MAX_PIXELS", "32768"))
-
-
 def shiftsum_chain_supported(widths, finest_pixels=0):
     """Dense inference: can the levels of these head widths (coarse to fine) run as chained GEMM launches + ONE completion launch
     (head_fused_gemm_nograd + head_shiftsum_chain_nograd)?  Every one must be a two-launch width (the one-launch kernel of C = 32
@@ -1130,9 +1064,6 @@ def head_shiftsum_item_nograd(item, scale, disp_scale, yl=None, scale_ll=1.0, cl
     return res[0]
 
 
-_HEAD_CHAIN_MULTI = os.environ.get("WMD_HEAD_CHAIN_MULTI", "1") != "0"   # 0: every level's first stage as a launch of its own
-
-
 def head_chain_multi_supported(widths):
     """Dense inference: may the first stages of these levels (coarse to fine) be postponed and run as ONE launch?"""
     l = _lib.lib()
@@ -1156,9 +1087,6 @@ def head_shiftsum_chain_nograd(items, scales, disp_scales, scale_ll=1.0, yl=None
     return res   # (the items' `keep` lists -- contiguous copies the GEMM launches read -- live in `items` until the caller drops them)
 
 
-_HEAD_PYRAMID = os.environ.get("WMD_HEAD_PYRAMID", "1") != "0"   # 0: the coarser levels' completions as a launch of their own
-
-
 def head_level_pyramid_supported(C_, B, H, W):
     """Dense inference: can the C = 32 level run its heads + synthesis AND the coarser levels' completions in one launch?"""
     return _HEAD_PYRAMID and os.environ.get("WMD_HEAD_STREAM", "1") != "0" and \
@@ -1179,10 +1107,6 @@ def head_level_pyramid_nograd(x, head_p, head_n, scale, disp_scale, items, scale
     a, _keep = _head_level_args(x, head_p, head_n, scale, yh, out, disp, disp_scale, clamp01)
     check(_lib.lib().wmd_head_level_pyramid_fwd(C.byref(a), arr, len(items), current_stream()), "wmd_head_level_pyramid_fwd")
     return res, (yh.unsqueeze(1), out, disp)
-
-
-_TRAIN_FUSED = os.environ.get("WMD_TRAIN_FUSED_HEADS", "1") != "0"   # 0: training forward of the heads on _StackedHeadsFn + idwt_haar
-_HEAD_CHAIN_ON = os.environ.get("WMD_HEAD_CHAIN", "1") != "0"
 
 
 def fused_train_supported(C_, H, W, has_ll):
@@ -1211,16 +1135,10 @@ class _FusedLevelFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, yl, x_gate, scale_hf, scale_ll, disp_scale, clamp01, *params):
         x = _c(x)
-        heads = [params[i:i + 4] for i in range(0, len(params), 4)]       # [+, -, (LL)]
-        has_ll = len(heads) == 3
-        order = ([2] if has_ll else []) + [0, 1]                            # channel order of mid: [LL, +, -]
-        offs, o = {}, 0
-        for k in order:
-            offs[k] = o
-            o += heads[k][0].shape[0]
+        heads, has_ll, _order, offs, _rows = _heads_layout(params)
         B, _, H, W = x.shape
         dev = x.device
-        mid = torch.empty((B, o, H, W), device=dev, dtype=torch.float32)
+        mid = torch.empty((B, sum(h[0].shape[0] for h in heads), H, W), device=dev, dtype=torch.float32)
         sp = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
         sn = torch.empty_like(sp)
         sl = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if has_ll else None
@@ -1232,8 +1150,8 @@ class _FusedLevelFn(torch.autograd.Function):
         yh, out, disp = res[0].squeeze(1), res[1], res[2]
         yl_ll = res[3] if has_ll else yh.new_empty(0)
         ctx.save_for_backward(x, mid, sp, sn, sl, out, *params)
-        ctx.meta = (x_gate, float(scale_hf), float(scale_ll), has_ll, order, offs)
-        ctx.cfg = (float(disp_scale), bool(clamp01))
+        ctx.meta = (x_gate, float(scale_hf), float(scale_ll))
+        ctx.cfg = (float(disp_scale), bool(clamp01), has_ll)
         ctx.mark_non_differentiable(mid)
         return yh, yl_ll, out, disp, mid
 
@@ -1242,8 +1160,7 @@ class _FusedLevelFn(torch.autograd.Function):
         l = _lib.lib()
         x, mid, sp, sn, sl, out = ctx.saved_tensors[:6]
         params = ctx.saved_tensors[6:]
-        has_ll = ctx.meta[3]
-        disp_scale, clamp01 = ctx.cfg
+        disp_scale, clamp01, has_ll = ctx.cfg
         B, _, H, W = x.shape
         # adjoint of the synthesis: d(out) + d(disp) through the clamp -> d(low-pass input), d(yh)
         d_lo = torch.empty((B, 1, H, W), device=x.device, dtype=torch.float32)

@@ -6,6 +6,7 @@ candidates once per problem signature on the live GPU and remembers the winner f
 (optionally across processes: WMD_TUNE_CACHE=/path/to/file.json).  WMD_AUTOTUNE=0 falls back to the
 library's built-in cost model.
 """
+import contextlib
 import json
 import os
 
@@ -115,6 +116,19 @@ def tune(key, taps, launch):
     if os.environ.get("WMD_TUNE_VERBOSE"):
         print("[wmd tuner] %s -> %s ksplit %d (%.1f us)" % (key, names[cfg - 1], ks, t * 1e3))
     return (cfg, ks)
+
+
+def pick(key, taps, launch, timing=None):
+    """The (cfg1, ksplit) choice of the forward and the data gradient: the remembered winner, else (0, 0) -- the library's cost
+    model -- inside a stream capture (nothing can be timed there), else tune().  timing: a context manager factory entered
+    around the sweep only (what the candidates are to be timed on, if not the caller's own operands)."""
+    choice = lookup(key)
+    if choice is None:
+        if torch.cuda.is_current_stream_capturing():
+            return (0, 0)
+        with timing() if timing else contextlib.nullcontext():
+            choice = tune(key, taps, launch)
+    return choice
 
 
 def choose(key, cands, launch):
