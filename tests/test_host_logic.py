@@ -778,6 +778,42 @@ def test_list_tile_query_agrees_with_the_planner_table():
         assert l.wmd_conv_list_tile_supported(th, tw) == 0, (th, tw)
 
 
+# (what the case is, wmd_conv_args fields, wmd_conv_fwd_workspace_floats as recorded from the library before the planner was
+#  restructured around explicit kernel families; pointers are stand-ins: the query dereferences none)
+_PLANNER_PINS = [
+    ("coarse split-K layer, library's choice", dict(B=1, H=6, W=20, C1=512, up1=1, C2=0, Cout=256), 491520),
+    ("coarse split-K layer, forced 4-way", dict(B=1, H=6, W=20, C1=512, up1=1, C2=0, Cout=256, tune_ksplit=4), 122880),
+    ("coarse split-K layer, forced 2 slices through the second-stage kernel",
+     dict(B=1, H=6, W=20, C1=512, up1=1, C2=0, Cout=256, tune_ksplit=-2), 61440),
+    ("coarse layer with concat, batch 12", dict(B=12, H=12, W=40, C1=256, up1=2, C2=256, Cout=256), 2949120),
+    ("work list on 8x16 tiles, one frame", dict(B=1, H=96, W=320, C1=32, up1=2, C2=64, Cout=32, in_mask=1, in_mask_2x2=1, out_mask=1,
+                                                out_tiles=1, out_tile_count=1, out_tile_h=8, out_tile_w=16), 5898240),
+    ("work list on 16x16 tiles, one frame", dict(B=1, H=48, W=160, C1=64, up1=2, C2=64, Cout=64, out_mask=1, out_tiles=1,
+                                                 out_tile_count=1, out_tile_h=16, out_tile_w=16), 3932160),
+    ("finest layer, batch 12: no split", dict(B=12, H=96, W=320, C1=32, up1=2, C2=64, Cout=32), 0),
+    ("1x1 layer: no split", dict(B=12, H=96, W=320, C1=32, up1=1, C2=0, Cout=64, ksize=1), 0),
+    ("refused: table index past the end", dict(B=1, H=6, W=20, C1=512, up1=1, C2=0, Cout=256, tune_cfg=1000), 0),
+    ("refused: work list over an impure channel layout", dict(B=1, H=96, W=320, C1=20, up1=1, C2=0, Cout=32, out_mask=1, out_tiles=1,
+                                                              out_tile_count=1, out_tile_h=8, out_tile_w=16), 0),
+]
+
+
+@pytest.mark.parametrize("what,fields,expected", _PLANNER_PINS, ids=[p[0] for p in _PLANNER_PINS])
+def test_conv_planner_workspace_answers_are_pinned(what, fields, expected, monkeypatch):
+    """plan_conv is host code: its choice of configuration and K split shows in wmd_conv_fwd_workspace_floats without a GPU.
+    (The per-call switches are cleared: they would force another choice.)"""
+    import ctypes as C
+    from wavelet_monodepth_amd import _lib
+    for name in ("WMD_CONV_CFG", "WMD_CONV_KSPLIT"):
+        monkeypatch.delenv(name, raising=False)
+    a = _lib.ConvArgs(ksize=3, pad_mode=1, act=1, x1=1, wp=1, y=1, wp_wino=1)
+    for k, v in fields.items():
+        setattr(a, k, v)
+    if a.C2:
+        a.x2 = 1
+    assert _lib.lib().wmd_conv_fwd_workspace_floats(C.byref(a)) == expected, what
+
+
 def test_bind_inputs_routes_are_decided_on_the_host():
     """decoder._bound (round 6): the route of a graph-mode forward is host logic -- buffers themselves / a recurring address set /
     copy -- and is decided before anything is launched.  Checked on stand-in tensors that record their copies (no GPU here)."""

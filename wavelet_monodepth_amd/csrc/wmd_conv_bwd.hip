@@ -19,9 +19,6 @@
 
 namespace wmd {
 
-
-int run_conv(const wmd_conv_args* g, int shift1, int H1, int W1, void* stream);
-
 // ------------------------------------------------------------------------------------------------
 // dgrad stage 2: adjoint of pad + concat + upsample
 // ------------------------------------------------------------------------------------------------

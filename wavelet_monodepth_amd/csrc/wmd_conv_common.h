@@ -1,5 +1,6 @@
-// Shared by the dense-decoder convolution kernels (wmd_conv_fwd.hip: direct implicit GEMM + Winograd on 16x16x4 MFMAs;
-// wmd_conv_wino32.hip: Winograd on 32x32x2 MFMAs): kernel argument block, XCD-aware work order, LDS-DMA wrappers.
+// Shared by the dense-decoder convolution kernels (wmd_conv_fwd.hip: direct implicit GEMM + Winograd on 16x16x4 MFMAs, the
+// configuration table, planner and launcher; wmd_conv_wino32[q].hip: Winograd on 32x32x2 MFMAs; wmd_conv_pack.hip: the weight
+// images): kernel argument block, fragment-image dimensions, XCD-aware work order, LDS-DMA wrappers.
 #pragma once
 #include "wmd_internal.h"
 
@@ -119,6 +120,11 @@ __device__ __forceinline__ f32x2 w32_pk_hi_f(f32x2 a, f32x2 b) { return f32x2{b[
 __device__ __forceinline__ f32x2 w32_pk_lo_ff(f32x2 a, f32x2 b) { return f32x2{b[0] - a[0], -a[1] - b[0]}; }
 __device__ __forceinline__ f32x2 w32_pk_hi_fl(f32x2 a, f32x2 b) { return f32x2{a[1] - b[0], a[1] - b[1]}; }
 #endif
+
+// Dimensions of a fragment-ordered weight image [ncot][nci4][taps or 16][64]: GEMM rows in tiles of 16, the reduction padded to 16
+// channels and counted in 4-channel K groups (rows / reduction = Cout / Cin forward, Cin / Cout for the data gradient).
+struct FragDims { int ncot, nci4; };
+inline FragDims frag_dims(int rows, int red) { return FragDims{(rows + 15) / 16, ((red + 15) / 16) * 4}; }
 
 struct ConvKArgs {
     const float* x1;
@@ -374,7 +380,10 @@ constexpr bool wino32q_has_list(int TH, int TW, int CK) { return CK == 8 && TH =
 
 // conv_wino32_kernel's flattened-staging instantiation needs every chunk inside one source tensor, one full-resolution
 // geometry; an input mask must live on that geometry too (same-size x1, or an upsampled x1 under a 2x2-constant mask, whose
-// low-resolution patch reads the mask at (2y, 2x)); everything else runs the GENERIC instantiation
+// low-resolution patch reads the mask at (2y, 2x)); everything else runs the GENERIC instantiation.
+// This is the LAUNCH-time choice of an instantiation, made on the kernel's arguments.  The planner's layer_is_pure (wmd_conv_fwd.hip)
+// decides earlier, on wmd_conv_args alone, which layers the quarter-position family and the work lists are offered: it cannot see
+// shift1 or the x1 extent, so the data-gradient's concat case and the same-size mask case are tested here only.
 inline bool wino32_pure(const ConvKArgs& a, int CK) {
     const bool mask_ok = !a.in_mask || (a.up1 == 2 ? a.in_mask_2x2 != 0 : (a.shift1 == 0 && a.H1 == a.H && a.W1 == a.W));
     return mask_ok && (a.Cin % CK) == 0 && (a.C2 == 0 || (a.C1 % CK) == 0) && (a.C2 == 0 || a.shift1 == 0);
@@ -382,6 +391,7 @@ inline bool wino32_pure(const ConvKArgs& a, int CK) {
 
 template <int TH, int TW, int WN, int CK>
 void launch_wino32(const ConvKArgs& a, dim3 grid, hipStream_t s);   // explicit instantiations: wmd_conv_wino32_table.inc
+int run_conv(const wmd_conv_args* g, int shift1, int H1, int W1, void* stream);   // wmd_conv_fwd.hip: plan and launch one convolution (data gradient: shift1 = 1)
 // Position `ti` of the concatenated per-frame tile lists -> the tile id; total = the number of listed tiles (sum of the counts).
 __device__ __forceinline__ int list_total(const int* __restrict__ tile_count, int B) {
     int n = 0;

@@ -805,68 +805,49 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_wino_kernel(const ConvKAr
     }
 }
 
-// Winograd weight image: the layout of conv_pack_kernel with 16 "taps" = transformed positions xi = 4a + b,
-//   U[a][b] = sum_{i,j} G[a][i] g[i][j] G[b][j],   G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]].
-__global__ void conv_pack_wino_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cout, int Cin, int ncot, int nci4,
-                                      int dgrad) {
-    const size_t total = (size_t)ncot * nci4 * 16 * 64;
-    const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int l = i & 63;
-        size_t r = i >> 6;
-        const int xi = r % 16;
-        r /= 16;
-        const int ci4 = r % nci4;
-        const int cot = r / nci4;
-        const int m = cot * 16 + (l & 15);
-        const int k = ci4 * 4 + (l >> 4);
-        float g[9];
-        bool ok;
-        if (!dgrad) {
-            ok = m < Cout && k < Cin;
-            for (int t = 0; t < 9; ++t) g[t] = ok ? w[((size_t)m * Cin + k) * 9 + t] : 0.f;
-        } else {
-            ok = m < Cin && k < Cout;
-            for (int t = 0; t < 9; ++t) g[t] = ok ? w[((size_t)k * Cin + m) * 9 + (8 - t)] : 0.f;
-        }
-        const int pa = xi / 4, pb = xi % 4;
-        float s = 0.f;
-        for (int ii = 0; ii < 3; ++ii)
-            for (int jj = 0; jj < 3; ++jj) s += G[pa][ii] * g[ii * 3 + jj] * G[pb][jj];
-        wp[i] = s;
-    }
-}
-
-// weights [Cout,Cin,k,k] -> fragment image [ncot][nci4][taps][64]; lane l holds
-// W[cot*16 + (l&15)][ci4*4 + (l>>4)][tap], zero outside.
-__global__ void conv_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cout, int Cin, int taps,
-                                 int ncot, int nci4, int dgrad) {
-    const size_t total = (size_t)ncot * nci4 * taps * 64;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int l = i & 63;
-        size_t r = i >> 6;
-        const int tap = r % taps;
-        r /= taps;
-        const int ci4 = r % nci4;
-        const int cot = r / nci4;
-        const int m = cot * 16 + (l & 15);  // GEMM row
-        const int k = ci4 * 4 + (l >> 4);   // GEMM reduction channel
-        float v = 0.f;
-        if (!dgrad) {
-            if (m < Cout && k < Cin) v = w[((size_t)m * Cin + k) * taps + tap];
-        } else {
-            // data gradient: rows are input channels, reduction runs over output channels, taps flipped
-            if (m < Cin && k < Cout) v = w[((size_t)k * Cin + m) * taps + (taps - 1 - tap)];
-        }
-        wp[i] = v;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// host side: configuration table + selection
+// host side: switches, configuration table, planner, launcher
 // ------------------------------------------------------------------------------------------------
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+
+// Every WMD_* environment switch of this file.  Read on every call (tests and tools set them between calls):
+static int sw_conv_cfg() { return env_int("WMD_CONV_CFG", -1); }          // force a table index (wmd_conv_args.tune_cfg - 1 wins)
+static int sw_conv_ksplit() { return env_int("WMD_CONV_KSPLIT", 0); }     // force a K split like wmd_conv_args.tune_ksplit (which wins)
+static int sw_conv_verbose() { return env_int("WMD_CONV_VERBOSE", 0); }   // one stderr line per launch (tools/make_profile_summary.py)
+// (-DWMD_STAMPS development builds only) device buffer of the per-block cycle stamps; mode bit 0: no output stores, bit 1: no activation
+static unsigned long long* sw_dbg_ptr() { const char* e = getenv("WMD_DBG_PTR"); return e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
+static int sw_dbg_mode() { return env_int("WMD_DBG_MODE", 0); }
+// Read once, at their first use, and fixed for the life of the process:
+static int sw_list_family() { static const int v = env_int("WMD_LIST_FAMILY", 18); return v; }      // 17: work lists prefer the position-halves kernel
+static int sw_splitk_ticket() { static const int v = env_int("WMD_SPLITK_TICKET", 1); return v; }   // 0: split-K is always summed by the second-stage kernels
+static int sw_x4() { static const int v = env_int("WMD_X4", 1); return v; }                         // 0: dword staging pieces everywhere (ConvKArgs.no_x4)
+static int sw_w32_coalesce() { static const int v = env_int("WMD_W32_COALESCE", 1); return v; }     // 0: conv_wino32_kernel stores 16-byte pieces, not whole lines
+static int sw_xcd_slab() { static const int v = env_int("WMD_XCD_SLAB", -1); return v; }            // 0 / 1: force the slab-per-XCD order of the 2-D grid off / on
+
+// The kernel families behind the table.  Everything the planner and the launcher decide per family is a predicate here.
+enum class ConvFamily {
+    Direct,    // conv_fwd_kernel: implicit GEMM over the filter taps (3x3 and 1x1)
+    Wino16,    // conv_wino_kernel: Winograd F(2x2,3x3) on 16x16x4 MFMAs
+    Wino32,    // conv_wino32_kernel (wmd_conv_wino32.hip): 32x32x2 MFMAs, two position halves per tile group
+    Wino32Q,   // conv_wino32q_kernel (wmd_conv_wino32q.hip): 32x32x2 MFMAs, four quarter-position waves per tile group
+};
+static bool fam_wino(ConvFamily f) { return f != ConvFamily::Direct; }   // transformed weight image (wp_wino), 3x3 semantics
+// the 32x32x2 kernels; they alone can finish a split-K tile in its last-arriving block (tickets) and know the slab-per-XCD order
+static bool fam_mfma32(ConvFamily f) { return f == ConvFamily::Wino32 || f == ConvFamily::Wino32Q; }
+static bool fam_needs_pure(ConvFamily f) { return f == ConvFamily::Wino32Q; }   // flattened staging only: every chunk inside one source tensor
+static int fam_resident_waves(ConvFamily f) { return f == ConvFamily::Wino32Q ? 12 : 8; }   // per CU: ~2 waves/SIMD of these register-heavy kernels, 3 of the quarter one
+// cost-model factor.  16x16x4: transforms + 1.5 LDS reads per MFMA (measured, not modelled); 32x32x2: fewer MFMAs on upsampled operands, lighter issue stream
+static double fam_model_factor(ConvFamily f) { return f == ConvFamily::Wino16 ? 1.3 : fam_mfma32(f) ? 0.8 : 1.0; }
+// cost-model weight on the MFMA work: the 32x32x2 families' former table tags 17 and 18 stood in for the 16 positions; the tuned choices rest on it
+static double fam_model_work(ConvFamily f) { return f == ConvFamily::Wino32 ? 17.0 / 16.0 : f == ConvFamily::Wino32Q ? 18.0 / 16.0 : 1.0; }
+constexpr int kListHalves = 17, kListQuarters = 18;   // the values WMD_LIST_FAMILY speaks in (anything else: no preference)
+
 struct ConvCfg {
-    int TH, TW, MR, NR, WM, WN, CK, TAPS;
+    ConvFamily family;
+    int taps, TH, TW, CK;           // filter taps served (1 or 9), pixel tile, channels per chunk
+    int co_block, px_cols, waves;   // per block: out channels, MFMA pixel columns, waves
+    int kpos;       // reduction positions per chunk channel: the taps, or 16 in the transformed domain
+    int groups;     // Winograd tile groups per block (16 tiles each on 16x16x4, 32 on 32x32x2 MFMAs); 0: direct
     int lds_bytes;
     void (*launch)(const ConvKArgs&, dim3, hipStream_t);
     const char* name;
@@ -879,7 +860,8 @@ static void launch_cfg(const ConvKArgs& a, dim3 grid, hipStream_t s) {
 
 #define WMD_CFG(TH, TW, MR, NR, WM, WN, CK, TAPS)                                                       \
     ConvCfg {                                                                                           \
-        TH, TW, MR, NR, WM, WN, CK, TAPS, (int)sizeof(float) * ConvTile<TH, TW, MR, NR, WM, WN, CK, TAPS>::LDS_FLOATS, \
+        ConvFamily::Direct, TAPS, TH, TW, CK, (WM) * (MR) * 16, (WN) * (NR) * 16, (WM) * (WN), TAPS, 0,  \
+            (int)sizeof(float) * ConvTile<TH, TW, MR, NR, WM, WN, CK, TAPS>::LDS_FLOATS,                \
             &launch_cfg<TH, TW, MR, NR, WM, WN, CK, TAPS>,                                              \
             "conv_fwd_kernel<" #TH "," #TW "," #MR "," #NR "," #WM "," #WN "," #CK "," #TAPS ">"         \
     }
@@ -889,25 +871,24 @@ static void launch_wino(const ConvKArgs& a, dim3 grid, hipStream_t s) {
     if (a.in_mask || a.out_mask) hipLaunchKernelGGL((conv_wino_kernel<TH, TW, MRW, WM, WN, CK, true>), grid, dim3(WM * WN * 64), 0, s, a);
     else hipLaunchKernelGGL((conv_wino_kernel<TH, TW, MRW, WM, WN, CK, false>), grid, dim3(WM * WN * 64), 0, s, a);
 }
-// Winograd entries reuse the table's fields: MR = out-channel tiles per wave, NR = 1 (a wave owns one group of 16
-// tiles = 64 pixels), TAPS = 16 transformed positions (this is what marks them).
+// conv_wino_kernel: MRW out-channel tiles per wave; a wave owns one group of 16 tiles = 64 pixels = 16 MFMA columns
 #define WMD_WINO(TH, TW, MRW, WM, WN, CK)                                                               \
     ConvCfg {                                                                                           \
-        TH, TW, MRW, 1, WM, WN, CK, 16, (int)sizeof(float) * WinoTile<TH, TW, MRW, WM, WN, CK>::LDS_FLOATS, \
+        ConvFamily::Wino16, 9, TH, TW, CK, (WM) * (MRW) * 16, (WN) * 16, (WM) * (WN), 16, WN,            \
+            (int)sizeof(float) * WinoTile<TH, TW, MRW, WM, WN, CK>::LDS_FLOATS,                         \
             &launch_wino<TH, TW, MRW, WM, WN, CK>, "conv_wino_kernel<" #TH "," #TW "," #MRW "," #WM "," #WN "," #CK ">" \
     }
 
-// conv_wino32_kernel (wmd_conv_wino32.hip) entries: TAPS = 17 marks the family (Winograd weight image, 3x3 semantics);
-// MR = 2 (a block's slab = 32 out channels), NR = 1 and WN = waves / WM so that the planner's block-shape arithmetic holds
+// conv_wino32_kernel (wmd_conv_wino32.hip): a 32-out-channel slab x WN tile groups of 32 MFMA columns, two waves per group
 #define WMD_W32_INST(TH, TW, WN, CK)                                                                                   \
-    ConvCfg{TH, TW, 2, 1, 1, (WN) * 2, CK, 17,                                                                         \
+    ConvCfg{ConvFamily::Wino32, 9, TH, TW, CK, 32, (WN) * 32, (WN) * 2, 16, WN,                                        \
             (int)sizeof(float) * (W32Tile<TH, TW, WN, CK>::LDS_FLOATS + W32Tile<TH, TW, WN, CK>::TAB_FLOATS),          \
             &launch_wino32<TH, TW, WN, CK>, "conv_wino32_kernel<" #TH "," #TW "," #WN "," #CK ">"},
 
-// conv_wino32q_kernel (wmd_conv_wino32q.hip, round 5) entries: TAPS = 18 marks the family (quarter-position waves: pure
-// channel chunking required; MASKED / LIST instantiations serve the block-sparse levels); MR = 2 (a block's slab = 32 out channels), WN = its four waves
+// conv_wino32q_kernel (wmd_conv_wino32q.hip, round 5): a 32-out-channel slab x one tile group, four quarter-position waves with
+// 16 MFMA columns each (MASKED / LIST instantiations serve the block-sparse levels)
 #define WMD_W32Q_INST(TH, TW, CK)                                                                                      \
-    ConvCfg{TH, TW, 2, 1, 1, 4, CK, 18,                                                                                \
+    ConvCfg{ConvFamily::Wino32Q, 9, TH, TW, CK, 32, 64, 4, 16, 1,                                                      \
             (int)sizeof(float) * (W32QTile<TH, TW, CK>::LDS_FLOATS + W32QTile<TH, TW, CK>::TAB_FLOATS),                \
             &launch_wino32q<TH, TW, CK>, "conv_wino32q_kernel<" #TH "," #TW "," #CK ">"},
 
@@ -991,29 +972,30 @@ struct ConvPlan {
     const ConvCfg* cfg;
     bool ticket;   // ksplit > 1 is finished inside the convolution (32x32x2 kernels) instead of by the second-stage kernel
     int ksplit, chunks_per_split, nchunks, tiles_x, tiles_y;
-    int H, W;  // problem as seen by the kernel (1x1 is flattened)
+    int H, W;      // problem as seen by the kernel (1x1 is flattened)
+    int cob;       // out-channel slabs per pixel tile
+    int bpc;       // blocks resident per CU
     size_t workspace_floats;
 };
-
-static int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 
 // Does table entry c run a work list (wmd_conv_args.out_tiles) on its own tile shape?  ONE predicate for the planner and for
 // wmd_conv_list_tile_supported (the two used to disagree on shapes only the quarter family can serve).  Both 32x32x2
 // families have LIST instantiations; where both serve a shape the quarter-position kernel takes it unless WMD_LIST_FAMILY=17
 // (forced = an explicit table index was asked for: either twin may run).
 static bool cfg_serves_list(const ConvCfg& c, bool forced) {
-    static const int list_family = env_int("WMD_LIST_FAMILY", 18);
-    const bool has17 = c.TAPS == 17 && wino32_has_list(c.TH, c.TW, c.WN / 2, c.CK);
-    const bool has18 = c.TAPS == 18 && wino32q_has_list(c.TH, c.TW, c.CK);
-    if (!has17 && !has18) return false;
+    const bool halves = c.family == ConvFamily::Wino32 && wino32_has_list(c.TH, c.TW, c.groups, c.CK);
+    const bool quarters = c.family == ConvFamily::Wino32Q && wino32q_has_list(c.TH, c.TW, c.CK);
+    if (!halves && !quarters) return false;
     if (forced) return true;
-    if (has17 && list_family == 18 && wino32q_has_list(c.TH, c.TW, c.CK)) return false;   // its quarter twin follows in the table
-    if (has18 && list_family == 17 && (wino32_has_list(c.TH, c.TW, 1, c.CK) || wino32_has_list(c.TH, c.TW, 2, c.CK))) return false;
+    if (halves && sw_list_family() == kListQuarters && wino32q_has_list(c.TH, c.TW, c.CK)) return false;   // its quarter twin follows in the table
+    if (quarters && sw_list_family() == kListHalves && (wino32_has_list(c.TH, c.TW, 1, c.CK) || wino32_has_list(c.TH, c.TW, 2, c.CK))) return false;
     return true;
+}
+
+// The planner's view of a "pure" layer: every CK-channel chunk inside one source tensor, and an input mask of an upsampled x1
+// constant on 2x2 blocks.  Required by the quarter-position family and by every work-list launch (see wino32_pure).
+static bool layer_is_pure(const wmd_conv_args* g, int CK) {
+    return (g->C1 + g->C2) % CK == 0 && (g->C2 == 0 || g->C1 % CK == 0) && !(g->in_mask && g->up1 == 2 && !g->in_mask_2x2);
 }
 
 static bool plan_conv(const wmd_conv_args* g, ConvPlan* plan, bool have_ws, size_t ws_floats) {
@@ -1021,94 +1003,71 @@ static bool plan_conv(const wmd_conv_args* g, ConvPlan* plan, bool have_ws, size
     const int Cin = g->C1 + g->C2;
     const int H = taps == 9 ? g->H : 1;
     const int W = taps == 9 ? g->W : g->H * g->W;
-    const int ncot = (g->Cout + 15) / 16;
-    const int force = g->tune_cfg > 0 ? g->tune_cfg - 1 : env_int("WMD_CONV_CFG", -1);
+    const int ncot = frag_dims(g->Cout, Cin).ncot;
+    const int force = g->tune_cfg > 0 ? g->tune_cfg - 1 : sw_conv_cfg();
     // tune_ksplit: k > 0 forces a k-way split, finished inside the convolution where the kernel can (32x32x2 families); k < 0 forces
     // |k| slices summed by the second-stage kernel (rounds 1-5; offered to the kernels that have both forms only)
-    const int force_raw = g->tune_ksplit != 0 ? g->tune_ksplit : env_int("WMD_CONV_KSPLIT", 0);
+    const int force_raw = g->tune_ksplit != 0 ? g->tune_ksplit : sw_conv_ksplit();
     const int force_ks = force_raw < 0 ? -force_raw : force_raw;
-    static const bool ticket_on = env_int("WMD_SPLITK_TICKET", 1) != 0;
+    const bool ticket_on = sw_splitk_ticket() != 0;
+    const size_t out_floats = (size_t)g->B * g->Cout * g->H * g->W;   // one split-K slice
     double best = 1e300;
     bool found = false;
-    plan->ticket = false;
     for (int i = 0; i < kNumCfgs; ++i) {
         const ConvCfg& c = kCfgs[i];
-        const bool wino = c.TAPS >= 16;
-        if (wino ? (taps != 9 || !g->wp_wino) : c.TAPS != taps) continue;
-        if ((g->in_mask || g->out_mask) && !wino) continue;   // block-sparse execution lives in the Winograd kernels
-        if (g->gate && wino) continue;                        // the output gate lives in the direct kernels (and the split-K reduce)
-        if (c.TAPS == 18 && (Cin % c.CK || (g->C2 > 0 && g->C1 % c.CK) || (g->in_mask && g->up1 == 2 && !g->in_mask_2x2)))
-            continue;                                         // quarter-position kernel: flattened staging of pure layers only (wino32_pure)
+        if (c.taps != taps || (fam_wino(c.family) && !g->wp_wino)) continue;
+        if ((g->in_mask || g->out_mask) && !fam_wino(c.family)) continue;   // block-sparse execution lives in the Winograd kernels
+        if (g->gate && fam_wino(c.family)) continue;                        // the output gate lives in the direct kernels (and the split-K reduce)
+        if (fam_needs_pure(c.family) && !layer_is_pure(g, c.CK)) continue;
         if (g->out_tiles) {   // work-list form: the LIST instantiations of the 32x32x2 kernels on the list's own tile shape
-            // (both families have one for 8 x 16 tiles: the quarter-position kernel unless WMD_LIST_FAMILY=17)
             if (!cfg_serves_list(c, force >= 0) || c.TH != g->out_tile_h || c.TW != g->out_tile_w) continue;
-            if (Cin % c.CK || (g->C2 > 0 && g->C1 % c.CK) || (g->in_mask && g->up1 == 2 && !g->in_mask_2x2)) continue;   // wino32_pure
+            if (!layer_is_pure(g, c.CK)) continue;
         }
         if (force >= 0 && force != i) continue;
-        const bool can_ticket = c.TAPS >= 17 && !g->gate && (double)g->Cout * g->H * g->W * 4.0 < 2147483647.0;   // (32-bit buffer offsets inside a frame)
+        const bool can_ticket = fam_mfma32(c.family) && !g->gate && (double)g->Cout * g->H * g->W * 4.0 < 2147483647.0;   // (32-bit buffer offsets inside a frame)
         if (force_raw < 0 && (!can_ticket || force_ks < 2)) continue;   // "-k" names the second-stage form of a kernel that has both
         const bool ticket = can_ticket && ticket_on && force_raw >= 0;
         const int tiles_x = (W + c.TW - 1) / c.TW, tiles_y = (H + c.TH - 1) / c.TH;
-        const long tiles = (long)g->B * tiles_x * tiles_y;
-        const int cob = (ncot + c.WM * c.MR - 1) / (c.WM * c.MR);
-        const long blocks = tiles * cob;
+        const int cob = (ncot * 16 + c.co_block - 1) / c.co_block;
+        const long blocks = (long)g->B * tiles_x * tiles_y * cob;
         const int nchunks = (Cin + c.CK - 1) / c.CK;
-        const int waves = c.WM * c.WN;
-        // blocks resident per CU: LDS (160 KiB) and ~2 waves/SIMD of these register-heavy kernels
-        int bpc = std::min(160 * 1024 / std::max(c.lds_bytes, 1), std::max(1, (c.TAPS == 18 ? 12 : 8) / waves));
-        bpc = std::max(bpc, 1);
-        const double block_macs_per_chunk = (double)(c.WM * c.MR * 16) * (c.WN * c.NR * 16) * c.CK * c.TAPS;   // MFMA work (Winograd: 16 positions x 16 tiles)
+        // blocks resident per CU: LDS (160 KiB) and the family's wave budget
+        const int bpc = std::max(1, std::min(160 * 1024 / std::max(c.lds_bytes, 1), std::max(1, fam_resident_waves(c.family) / c.waves)));
+        auto store = [&](int ks, int cps) {
+            *plan = ConvPlan{&c, ticket, ks, cps, nchunks, tiles_x, tiles_y, H, W, cob, bpc, ks > 1 ? (size_t)ks * out_floats : 0};
+            found = true;
+        };
         if (g->out_tiles) {
             // the device picks the split (list_ksplit) up to ksmax slices = gridDim.z: as many as could matter if every
             // slice of every possible item had to find a workgroup slot (a batch of frames never splits)
             // (measured at one frame: leaving the 8- and 12-chunk layers of the finest level unsplit -- no second pass -- cost
             //  20.4 + 24.7 us against 12.4 + 4.9 + 16.4 + 6.7 us split and reduced: the split stays on offer wherever it fits)
             const int ksmax = (int)std::max<long>(1, std::min<long>(std::min(nchunks / 2, 16), 2L * kNumCU * bpc / std::max<long>(blocks, 1)));
-            const size_t need = ksmax > 1 ? (size_t)ksmax * g->B * g->Cout * g->H * g->W : 0;
-            if (ksmax > 1 && (!have_ws || need > ws_floats)) continue;
-            found = true;
-            plan->cfg = &c;
-            plan->ticket = ticket;
-            plan->ksplit = ksmax;
-            plan->chunks_per_split = nchunks;
-            plan->nchunks = nchunks;
-            plan->tiles_x = tiles_x;
-            plan->tiles_y = tiles_y;
-            plan->H = H;
-            plan->W = W;
-            plan->workspace_floats = need;
+            if (ksmax > 1 && (!have_ws || (size_t)ksmax * out_floats > ws_floats)) continue;
+            store(ksmax, nchunks);
             break;
         }
+        // MFMA work of a block per chunk (Winograd: 16 positions x 16 tiles)
+        const double block_macs_per_chunk = (double)c.co_block * c.px_cols * c.CK * c.kpos * fam_model_work(c.family);
         for (int ks = 1; ks <= 32; ++ks) {
             if (force_ks > 0 ? ks != force_ks : (ks & (ks - 1)) != 0 || ks > 16) continue;  // model: powers of two
             if (ks > 1 && (!have_ws || nchunks < ks)) continue;
             const int cps = (nchunks + ks - 1) / ks;
             const int ks_eff = (nchunks + cps - 1) / cps;
-            if (ks > 1 && (size_t)ks_eff * g->B * g->Cout * g->H * g->W > ws_floats) continue;
+            if (ks > 1 && (size_t)ks_eff * out_floats > ws_floats) continue;
             const long nblk = blocks * ks_eff;
             const long rounds = (nblk + (long)kNumCU * bpc - 1) / ((long)kNumCU * bpc);
             // waves sharing one CU's four matrix pipes in a full round
-            const double conc = std::min<double>(bpc, (double)nblk / kNumCU) * waves;
+            const double conc = std::min<double>(bpc, (double)nblk / kNumCU) * c.waves;
             const double rate = 128.0 * std::min(1.0, conc / 4.0);  // MAC / clk / CU
             double per_cu_blocks = (double)rounds * std::min<double>(bpc, std::max(1.0, (double)nblk / kNumCU / rounds));
             double cycles = per_cu_blocks * block_macs_per_chunk * cps / std::max(rate, 1.0);
             cycles += 3000.0 * rounds;            // prologue/epilogue per block round
-            if (c.TAPS == 16) cycles *= 1.3;      // transforms + 1.5 LDS reads per MFMA: measured, not modelled
-            if (c.TAPS >= 17) cycles *= 0.8;      // 32x32x2 forms: fewer MFMAs on upsampled operands, lighter issue stream
+            cycles *= fam_model_factor(c.family);
             if (ks_eff > 1) cycles += ticket ? 2500.0 : 6000.0;     // the last block's finish / the reduce pass launch
             if (cycles < best) {
                 best = cycles;
-                found = true;
-                plan->cfg = &c;
-                plan->ticket = ticket;
-                plan->ksplit = ks_eff;
-                plan->chunks_per_split = cps;
-                plan->nchunks = nchunks;
-                plan->tiles_x = tiles_x;
-                plan->tiles_y = tiles_y;
-                plan->H = H;
-                plan->W = W;
-                plan->workspace_floats = ks_eff > 1 ? (size_t)ks_eff * g->B * g->Cout * g->H * g->W : 0;
+                store(ks_eff, cps);
             }
         }
     }
@@ -1118,8 +1077,6 @@ static bool plan_conv(const wmd_conv_args* g, ConvPlan* plan, bool have_ws, size
 }  // namespace wmd
 
 using namespace wmd;
-
-extern "C" int wmd_head_fused_fwd(const wmd_head_fused_args* g, void* stream);
 
 extern "C" int wmd_head_fused_multi_fwd(const wmd_head_fused_args* levels, int n_levels, void* stream) {
     if (!levels || n_levels < 1 || n_levels > 3) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_multi_fwd: 1..3 levels (got %d)", n_levels);
@@ -1189,8 +1146,8 @@ extern "C" int wmd_head_fused_fwd(const wmd_head_fused_args* g, void* stream) {
     a.up1 = 1;
     a.act = WMD_ACT_LEAKY;
     a.slope = g->slope;
-    a.nci4 = ((g->C + 15) / 16) * 4;
-    a.ncot = rows / 16;
+    a.nci4 = frag_dims(rows, g->C).nci4;
+    a.ncot = frag_dims(rows, g->C).ncot;
     a.nchunks = g->C >= 128 ? g->C / 32 : 1;   // C = 32 / 64: the whole reduction is one LDS-resident chunk
     a.ksplit = 1;
     a.chunks_per_split = a.nchunks;
@@ -1231,161 +1188,6 @@ extern "C" int wmd_head_fused_fwd(const wmd_head_fused_args* g, void* stream) {
 extern "C" int wmd_conv_num_configs(void) { return kNumCfgs; }
 extern "C" const char* wmd_conv_config_name(int i) { return (i >= 0 && i < kNumCfgs) ? kCfgs[i].name : nullptr; }
 
-extern "C" size_t wmd_conv_packed_weight_floats(int Cout, int Cin, int ksize) {
-    const int taps = ksize == 3 ? 9 : 1;
-    // rows and reduction are both padded to 16, so the forward and the dgrad image have the same size
-    const size_t ncot = (Cout + 15) / 16;
-    const size_t nci4 = ((Cin + 15) / 16) * 4;
-    return ncot * nci4 * taps * 64;
-}
-
-static int pack_common(const float* w, float* wp, int Cout, int Cin, int ksize, int dgrad, void* stream) {
-    if (!w || !wp) return fail(WMD_ERR_BAD_ARG, "wmd_conv_pack_weights: null pointer");
-    if (Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3))
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_conv_pack_weights: Cout=%d Cin=%d ksize=%d", Cout, Cin, ksize);
-    const int taps = ksize == 3 ? 9 : 1;
-    const int rows = dgrad ? Cin : Cout, red = dgrad ? Cout : Cin;
-    const int ncot = (rows + 15) / 16, nci4 = ((red + 15) / 16) * 4;
-    const size_t total = (size_t)ncot * nci4 * taps * 64;
-    const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-    ProfScope prof("conv_pack_kernel", 0.0, 8.0 * total, (hipStream_t)stream);
-    hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, taps, ncot,
-                       nci4, dgrad);
-    return check_launch("conv_pack_kernel");
-}
-
-extern "C" int wmd_conv_pack_weights(const float* w, float* wp, int Cout, int Cin, int ksize, void* stream) {
-    return pack_common(w, wp, Cout, Cin, ksize, 0, stream);
-}
-extern "C" int wmd_conv_pack_weights_dgrad(const float* w, float* wp, int Cout, int Cin, int ksize, void* stream) {
-    return pack_common(w, wp, Cout, Cin, ksize, 1, stream);
-}
-
-extern "C" size_t wmd_conv_packed_weight_floats_wino(int Cout, int Cin) {
-    if (Cout <= 0 || Cin <= 0) return 0;
-    const size_t ncot = (Cout + 15) / 16;
-    const size_t nci4 = ((Cin + 15) / 16) * 4;
-    return ncot * nci4 * 16 * 64;
-}
-
-extern "C" int wmd_conv_pack_weights_wino(const float* w, float* wp, int Cout, int Cin, int dgrad, void* stream) {
-    if (!w || !wp) return fail(WMD_ERR_BAD_ARG, "wmd_conv_pack_weights_wino: null pointer");
-    if (Cout <= 0 || Cin <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_conv_pack_weights_wino: Cout=%d Cin=%d", Cout, Cin);
-    const int rows = dgrad ? Cin : Cout, red = dgrad ? Cout : Cin;
-    const int ncot = (rows + 15) / 16, nci4 = ((red + 15) / 16) * 4;
-    const size_t total = (size_t)ncot * nci4 * 16 * 64;
-    ProfScope prof("conv_pack_wino_kernel", 0.0, 8.0 * total, (hipStream_t)stream);
-    hipLaunchKernelGGL(conv_pack_wino_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, w,
-                       wp, Cout, Cin, ncot, nci4, dgrad ? 1 : 0);
-    return check_launch("conv_pack_wino_kernel");
-}
-
-// ------------------------------------------------------------------------------------------------
-// every weight image of a set of filters in one launch (a training step repacks all of them after each optimizer update:
-// as ~50 separate 5-10 us launches that was 9 % of the decoder's forward + backward).
-// One workgroup = one 16 x 16 (Cout x Cin) tile of one filter, all taps: the 16 rows are 16*taps contiguous floats each,
-// staged once in LDS, and every requested image of that tile -- forward and data-gradient fragment order, direct and
-// Winograd -- is a contiguous 4*taps*64 (4*16*64) float run written from there.  Same arithmetic, in the same order, as
-// conv_pack_kernel / conv_pack_wino_kernel: the images are bit-identical.
-// ------------------------------------------------------------------------------------------------
-constexpr int kPackManyMax = 40;
-struct PackManyItem {
-    const float* w;
-    float *fwd, *dgrad, *wfwd, *wdgrad;
-    int Cout, Cin, taps, tile0;   // tile0 = index of this item's first tile in the launch
-};
-struct PackManyArgs {
-    int n, tiles;
-    PackManyItem it[kPackManyMax];
-};
-
-__global__ __launch_bounds__(256) void conv_pack_many_kernel(const PackManyArgs a) {
-    __shared__ float s[16 * 144];
-    const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
-    const int tid = threadIdx.x;
-    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        int k = 0;
-        while (k + 1 < a.n && a.it[k + 1].tile0 <= tile) ++k;
-        const PackManyItem& it = a.it[k];
-        const int taps = it.taps, Cout = it.Cout, Cin = it.Cin;
-        const int nb = (Cin + 15) / 16, na = (Cout + 15) / 16;
-        const int ta = (tile - it.tile0) / nb, tb = (tile - it.tile0) % nb;   // Cout tile, Cin tile
-        const int row_len = 16 * taps;
-        __syncthreads();
-        {
-            const int r = tid >> 4, m = ta * 16 + r;
-            const float* src = it.w + ((size_t)m * Cin + tb * 16) * taps;
-            const int valid = m < Cout ? (min(16, Cin - tb * 16)) * taps : 0;
-            for (int c = tid & 15; c < row_len; c += 16) s[r * 144 + c] = c < valid ? src[c] : 0.f;
-        }
-        __syncthreads();
-        const size_t fbase = ((size_t)ta * nb * 4 + 4 * tb) * 64;   // x taps (or x 16): first float of the tile's run, forward order
-        const size_t dbase = ((size_t)tb * na * 4 + 4 * ta) * 64;   // data-gradient order: rows = Cin tile, reduction = Cout tile
-        const int n_direct = 4 * taps * 64;
-        if (it.fwd)
-            for (int i = tid; i < n_direct; i += 256) {
-                const int l = i & 63, r = i >> 6, tap = r % taps, q = r / taps;
-                it.fwd[fbase * taps + i] = s[(l & 15) * 144 + (q * 4 + (l >> 4)) * taps + tap];
-            }
-        if (it.dgrad)
-            for (int i = tid; i < n_direct; i += 256) {
-                const int l = i & 63, r = i >> 6, tap = r % taps, q = r / taps;
-                it.dgrad[dbase * taps + i] = s[(q * 4 + (l >> 4)) * 144 + (l & 15) * taps + (taps - 1 - tap)];
-            }
-        if (taps == 9 && (it.wfwd || it.wdgrad))
-            for (int i = tid; i < 4 * 16 * 64; i += 256) {
-                const int l = i & 63, r = i >> 6, xi = r & 15, q = r >> 4;
-                const int pa = xi >> 2, pb = xi & 3;
-                if (it.wfwd) {
-                    const float* g = &s[(l & 15) * 144 + (q * 4 + (l >> 4)) * 9];
-                    float u = 0.f;
-                    for (int ii = 0; ii < 3; ++ii)
-                        for (int jj = 0; jj < 3; ++jj) u += G[pa][ii] * g[ii * 3 + jj] * G[pb][jj];
-                    it.wfwd[fbase * 16 + i] = u;
-                }
-                if (it.wdgrad) {
-                    const float* g = &s[(q * 4 + (l >> 4)) * 144 + (l & 15) * 9];
-                    float u = 0.f;
-                    for (int ii = 0; ii < 3; ++ii)
-                        for (int jj = 0; jj < 3; ++jj) u += G[pa][ii] * g[8 - (ii * 3 + jj)] * G[pb][jj];
-                    it.wdgrad[dbase * 16 + i] = u;
-                }
-            }
-    }
-}
-
-extern "C" int wmd_conv_pack_many(const wmd_pack_item* items, int n, void* stream) {
-    if (n < 0 || (n && !items)) return fail(WMD_ERR_BAD_ARG, "wmd_conv_pack_many: null items");
-    for (int i = 0; i < n; ++i) {
-        const wmd_pack_item& p = items[i];
-        if (!p.w) return fail(WMD_ERR_BAD_ARG, "wmd_conv_pack_many: item %d has no weights", i);
-        if (p.Cout <= 0 || p.Cin <= 0 || (p.ksize != 1 && p.ksize != 3))
-            return fail(WMD_ERR_BAD_SHAPE, "wmd_conv_pack_many: item %d Cout=%d Cin=%d ksize=%d", i, p.Cout, p.Cin, p.ksize);
-        if (p.ksize != 3 && (p.wino_fwd || p.wino_dgrad))
-            return fail(WMD_ERR_BAD_ARG, "wmd_conv_pack_many: item %d asks for a Winograd image of a %dx%d filter", i, p.ksize, p.ksize);
-    }
-    for (int i0 = 0; i0 < n; i0 += kPackManyMax) {
-        PackManyArgs a;
-        a.n = std::min(kPackManyMax, n - i0);
-        int tiles = 0;
-        double floats = 0;
-        for (int i = 0; i < a.n; ++i) {
-            const wmd_pack_item& p = items[i0 + i];
-            a.it[i] = PackManyItem{p.w, p.fwd, p.dgrad, p.wino_fwd, p.wino_dgrad, p.Cout, p.Cin, p.ksize == 3 ? 9 : 1, tiles};
-            tiles += ((p.Cout + 15) / 16) * ((p.Cin + 15) / 16);
-            const double img = (double)wmd_conv_packed_weight_floats(p.Cout, p.Cin, p.ksize);
-            floats += (double)p.Cout * p.Cin * (p.ksize == 3 ? 9 : 1) + img * ((p.fwd != nullptr) + (p.dgrad != nullptr)) +
-                      img / 9 * 16 * ((p.wino_fwd != nullptr) + (p.wino_dgrad != nullptr));
-        }
-        a.tiles = tiles;
-        ProfScope prof("conv_pack_many_kernel", 0.0, 4.0 * floats, (hipStream_t)stream);
-        hipLaunchKernelGGL(conv_pack_many_kernel, dim3(std::min(tiles, 8192)), dim3(256), 0, (hipStream_t)stream, a);
-        int rc = check_launch("conv_pack_many_kernel");
-        if (rc) return rc;
-    }
-    return WMD_OK;
-}
-
 extern "C" int wmd_conv_list_tile_supported(int tile_h, int tile_w) {
     for (int i = 0; i < kNumCfgs; ++i) {
         const ConvCfg& c = kCfgs[i];
@@ -1421,12 +1223,7 @@ static int validate_conv(const wmd_conv_args* g, const char* who) {
 extern "C" size_t wmd_conv_fwd_workspace_floats(const wmd_conv_args* g) {
     if (!g || g->B <= 0 || g->Cout <= 0) return 0;
     ConvPlan plan;
-    if (!plan_conv(g, &plan, true, (size_t)-1)) return 0;
-    return plan.workspace_floats;
-}
-
-namespace wmd {
-int run_conv(const wmd_conv_args* g, int shift1, int H1, int W1, void* stream);
+    return plan_conv(g, &plan, true, (size_t)-1) ? plan.workspace_floats : 0;
 }
 
 extern "C" int wmd_conv_fwd(const wmd_conv_args* g, void* stream) {
@@ -1436,7 +1233,9 @@ extern "C" int wmd_conv_fwd(const wmd_conv_args* g, void* stream) {
 }
 
 // The ticket ring of the in-kernel split-K finish: 1 Mi counters, zero-filled once (outside any capture), handed out in
-// consecutive regions.
+// consecutive regions: one self-resetting counter per (tile, slab) item (the last arriver of an item re-arms its counter, so a
+// region is all zero whenever no launch is using it; consecutive launches take consecutive regions, so launches in flight on
+// different streams -- and the nodes of a captured graph, whose region is part of the captured arguments -- never share one).
 static int* ticket_region(size_t items, hipStream_t stream) {
     constexpr size_t kRing = 1u << 20;
     static int* ring = nullptr;
@@ -1463,10 +1262,92 @@ static int* ticket_region(size_t items, hipStream_t stream) {
     return r;
 }
 
+// One launch, in pieces.  fill_args: wmd_conv_args + plan -> the kernel's argument block (tickets, y_final and the item order: below)
+static void fill_args(const wmd_conv_args* g, const ConvPlan& plan, int shift1, int H1, int W1, ConvKArgs& a) {
+    const bool k3 = plan.cfg->taps == 9;   // (a 1x1 layer runs on the flattened image)
+    const FragDims img = frag_dims(g->Cout, g->C1 + g->C2);
+    memset(&a, 0, sizeof(a));
+    a.x1 = g->x1, a.x2 = g->C2 > 0 ? g->x2 : nullptr, a.bias = g->bias;
+    a.wp = fam_wino(plan.cfg->family) ? g->wp_wino : g->wp;
+    a.y = plan.ksplit > 1 ? g->workspace : g->y;
+    a.B = g->B, a.H = plan.H, a.W = plan.W;
+    a.C1 = g->C1, a.C2 = g->C2, a.Cin = g->C1 + g->C2, a.Cout = g->Cout;
+    a.up1 = k3 ? g->up1 : 1, a.shift1 = shift1, a.H1 = k3 ? H1 : 1, a.W1 = k3 ? W1 : H1 * W1;
+    a.pad_mode = g->pad_mode, a.act = g->act, a.slope = g->slope;
+    a.tiles_x = plan.tiles_x, a.tiles_y = plan.tiles_y, a.nci4 = img.nci4, a.ncot = img.ncot;
+    a.nchunks = plan.nchunks, a.ksplit = plan.ksplit, a.chunks_per_split = plan.chunks_per_split;
+    a.no_x4 = sw_x4() == 0, a.st_coalesce = sw_w32_coalesce();
+#ifdef WMD_STAMPS
+    a.dbg = sw_dbg_ptr(), a.dbg_mode = sw_dbg_mode();
+#endif
+    if (g->out_tiles) a.tile_list = g->out_tiles, a.tile_count = g->out_tile_count, a.ksmax = plan.ksplit, a.list_slots = kNumCU * plan.bpc;
+    a.gate = g->gate, a.gate_act = g->gate_act, a.gate_slope = g->gate_slope;
+    a.in_mask = g->in_mask, a.out_mask = g->out_mask, a.in_mask_2x2 = g->in_mask_2x2;
+}
+
+// Item order and grid.  Slabs of a tile back to back on one XCD (they share the gathered input patch) while the whole weight
+// image stays resident in an XCD's 4 MB L2; for the coarse layers, whose weights are larger than that and whose patches are
+// small, the tiles of one slab run together instead (they share that slab's weights) -- the 2-D grid.
+static dim3 choose_grid(const wmd_conv_args* g, const ConvPlan& plan, int H1, int W1, ConvKArgs& a) {
+    const int cob = plan.cob, xs = sw_xcd_slab();
+    const double wbytes = (double)a.ncot * 16 * a.nci4 * 4 * plan.cfg->kpos * 4;
+    const bool tile_major = g->out_tiles || (cob > 1 && wbytes <= 3.0 * 1024 * 1024);   // (list items are always (tile, slab) pairs)
+    a.cob = tile_major ? cob : 0;
+    // the coarse layers' 2-D grid: a slab per XCD when the slabs divide over the eight XCDs, every z-slice starts on XCD 0 and the
+    // weight image outweighs the input maps (they are then what each XCD re-reads; WMD_XCD_SLAB=0/1 forces it off / on)
+    const size_t tiles_n = (size_t)g->B * plan.tiles_x * plan.tiles_y;
+    const double in_bytes = 4.0 * g->B * ((double)g->C1 * H1 * W1 + (double)g->C2 * g->H * g->W);
+    const bool fits = !tile_major && fam_mfma32(plan.cfg->family) && cob % 8 == 0 && (tiles_n * cob) % 8 == 0;
+    a.xcd_slab = fits && (xs >= 0 ? xs != 0 : wbytes > in_bytes) ? 1 : 0;
+    return dim3((unsigned)(tiles_n * (tile_major ? cob : 1)), tile_major ? 1u : (unsigned)cob, (unsigned)plan.ksplit);
+}
+
+// The launch with its profiler scope.
+static int launch_conv(const wmd_conv_args* g, const ConvPlan& plan, const ConvKArgs& a, dim3 grid, hipStream_t s) {
+    const ConvCfg& c = *plan.cfg;
+    if (sw_conv_verbose())
+        // (sig = the autotuner's problem signature: profiles key the counters of a launch by it, see tools/make_profile_summary.py)
+        fprintf(stderr, "[wmd] conv %dx%d C%d+%d->%d k%d: cfg %s grid %u,%u,%u block %d sig conv|%d|%d|%d|%d|%d|%d|%d|%d%s\n", g->H, g->W, g->C1,
+                g->C2, g->Cout, g->ksize, c.name, grid.x, grid.y, grid.z, c.waves * 64, g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout,
+                g->ksize, a.shift1 ? "|dgrad" : "");
+    const double pix = (double)g->B * g->H * g->W;
+    {
+        // algorithmic work: 2*Cin*k*k*Cout FLOP per output pixel; bytes: inputs + weights + outputs once
+        ProfScope prof(c.name, 2.0 * a.Cin * c.taps * g->Cout * pix,
+                       4.0 * (pix * g->C1 / (a.up1 * a.up1) + pix * g->C2 + (double)a.Cin * c.taps * g->Cout + pix * g->Cout), s);
+        if (c.family == ConvFamily::Wino16) prof.mfma(2.0 * a.Cin * 9 * g->Cout * pix / 2.25);
+        if (fam_mfma32(c.family)) {   // 32x32x2 MFMAs of 4096 FLOP: per block its tile groups x chunks x K-steps x positions
+            const int n_up = (wino32_pure(a, c.CK) && a.up1 == 2) ? a.C1 / c.CK : 0;
+            prof.mfma(4096.0 * grid.x * grid.y * c.groups * (c.CK / 2) * (9.0 * n_up + 16.0 * (plan.nchunks - n_up)));
+        }
+        c.launch(a, grid, s);
+    }
+    return check_launch("conv_fwd_kernel");
+}
+
+// The split-K finish of a launch that did not finish inside the convolution: the work list's own reduce, or the plain one.
+static int finish_splitk(const wmd_conv_args* g, const ConvPlan& plan, const ConvKArgs& a, hipStream_t s) {
+    if (plan.ksplit <= 1) return WMD_OK;   // (a work list with ksmax = 1: the device can never split, no second pass)
+    if (g->out_tiles) {
+        const int ntiles = g->B * plan.tiles_x * plan.tiles_y;
+        ProfScope prof("conv_splitk_reduce_list_kernel", 0.0, 0.0, s);
+        hipLaunchKernelGGL(conv_splitk_reduce_list_kernel, dim3(ntiles, (g->Cout + kRedCh - 1) / kRedCh), dim3(256), 0, s, g->workspace, g->bias, g->y,
+                           g->out_tiles, g->out_tile_count, g->out_mask, g->B, g->Cout, g->H, g->W, plan.cfg->TH, plan.cfg->TW, plan.tiles_x,
+                           plan.tiles_y, plan.cob, plan.nchunks, plan.ksplit, a.list_slots, g->act, g->slope);
+        return check_launch("conv_splitk_reduce_list_kernel");
+    }
+    const size_t n = (size_t)g->B * g->Cout * g->H * g->W;
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
+    ProfScope prof("conv_splitk_reduce_kernel", (double)n * plan.ksplit, 4.0 * n * (plan.ksplit + 1), s);
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, g->workspace, g->bias, g->y, n, (size_t)g->H * g->W, g->Cout,
+                       plan.ksplit, g->act, g->slope, g->gate, g->gate_act, g->gate_slope, g->out_mask);
+    return check_launch("conv_splitk_reduce_kernel");
+}
+
 // Shared by the forward pass and by the data-gradient pass (which feeds dz through the same kernel with
 // transposed/flipped weights, shift1 = 1 and an (H+2) x (W+2) logical extent).
 int wmd::run_conv(const wmd_conv_args* g, int shift1, int H1, int W1, void* stream) {
-    int st = WMD_OK;
+    hipStream_t s = (hipStream_t)stream;
     // buffer descriptors address one image of a source tensor with 32-bit byte offsets below 2^31
     const double lim = 2147483647.0;
     if ((double)g->C1 * H1 * W1 * 4 > lim || (double)g->C2 * g->H * g->W * 4 > lim ||
@@ -1475,135 +1356,15 @@ int wmd::run_conv(const wmd_conv_args* g, int shift1, int H1, int W1, void* stre
         return fail(WMD_ERR_UNSUPPORTED, "wmd_conv: a per-image tensor slice or the weight image exceeds 2 GiB");
     ConvPlan plan;
     if (!plan_conv(g, &plan, g->workspace != nullptr, g->workspace_floats)) return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_fwd: no kernel configuration");
-    const ConvCfg& c = *plan.cfg;
-    const bool wino = c.TAPS >= 16;           // Winograd configuration (16: 16x16x4 kernels, 17: 32x32x2 kernels): transformed weight image, 3x3 semantics
-    const int taps = wino ? 9 : c.TAPS;
+    if (plan.cfg->taps == 1 && g->up1 == 2) return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_fwd: 1x1 with upsampled input");
     ConvKArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x1 = g->x1;
-    a.x2 = g->C2 > 0 ? g->x2 : nullptr;
-    a.wp = wino ? g->wp_wino : g->wp;
-    a.bias = g->bias;
-    a.B = g->B;
-    a.H = plan.H;
-    a.W = plan.W;
-    a.C1 = g->C1;
-    a.C2 = g->C2;
-    a.Cin = g->C1 + g->C2;
-    a.Cout = g->Cout;
-    a.up1 = taps == 9 ? g->up1 : 1;
-    if (taps == 1 && g->up1 == 2) return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_fwd: 1x1 with upsampled input");
-    a.shift1 = shift1;
-    a.H1 = taps == 9 ? H1 : 1;
-    a.W1 = taps == 9 ? W1 : H1 * W1;
-    a.pad_mode = g->pad_mode;
-    a.act = g->act;
-    a.slope = g->slope;
-    a.tiles_x = plan.tiles_x;
-    a.tiles_y = plan.tiles_y;
-    a.nci4 = ((a.Cin + 15) / 16) * 4;
-    a.ncot = (g->Cout + 15) / 16;
-    a.nchunks = plan.nchunks;
-    a.ksplit = plan.ksplit;
-    a.chunks_per_split = plan.chunks_per_split;
-    a.y = plan.ksplit > 1 ? g->workspace : g->y;
-    // split-K finished inside the convolution: one self-resetting ticket counter per (tile, slab) item from the library's ring
-    // (the last arriver of an item re-arms its counter, so a region is all zero whenever no launch is using it; consecutive
-    // launches take consecutive regions, so launches in flight on different streams -- and the nodes of a captured graph, whose
-    // region is part of the captured arguments -- never share one).  No ring (allocation refused, or the first use would fall
-    // inside a stream capture): the second-stage kernels run as before.
-    bool ticket = plan.ticket && plan.ksplit > 1;
-    if (ticket) {
-        const int cob_t = (a.ncot + c.WM * c.MR - 1) / (c.WM * c.MR);
-        const size_t items = (size_t)g->B * plan.tiles_x * plan.tiles_y * cob_t;
-        a.tickets = ticket_region(items, (hipStream_t)stream);
-        if (!a.tickets) ticket = false;
-        else a.y_final = g->y;
-    }
-    static const int no_x4 = env_int("WMD_X4", 1) == 0;
-    a.no_x4 = no_x4;
-    static const int st_coalesce = env_int("WMD_W32_COALESCE", 1);
-    a.st_coalesce = st_coalesce;
-#ifdef WMD_STAMPS
-    if (const char* e = getenv("WMD_DBG_PTR")) a.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
-    a.dbg_mode = env_int("WMD_DBG_MODE", 0);
-#endif
-    const bool list = g->out_tiles != nullptr;
-    if (list) {
-        a.tile_list = g->out_tiles;
-        a.tile_count = g->out_tile_count;
-        a.ksmax = plan.ksplit;
-        a.list_slots = kNumCU * std::max(1, std::min(160 * 1024 / std::max(c.lds_bytes, 1), std::max(1, (c.TAPS == 18 ? 12 : 8) / (c.WM * c.WN))));
-        a.y_final = g->y;
-    }
-    if (ticket) a.y_final = g->y;
-    a.gate = g->gate;
-    a.gate_act = g->gate_act;
-    a.gate_slope = g->gate_slope;
-    a.in_mask = g->in_mask;
-    a.out_mask = g->out_mask;
-    a.in_mask_2x2 = g->in_mask_2x2;
-    if ((g->out_mask || g->in_mask) && !wino)
-        return fail(WMD_ERR_UNSUPPORTED, "wmd_conv: masks (block-sparse execution) need a 3x3 layer and the Winograd weight image (wp_wino)");
-    const int cob = (a.ncot + c.WM * c.MR - 1) / (c.WM * c.MR);
-    // Item order: slabs of a tile back to back on one XCD (they share the gathered input patch) while the whole weight image
-    // stays resident in an XCD's 4 MB L2; for the coarse layers, whose weights are larger than that and whose patches are
-    // small, the tiles of one slab run together instead (they share that slab's weights) -- the 2-D grid.
-    const double wbytes = (double)a.ncot * 16 * a.nci4 * 4 * (wino ? 16 : taps) * 4;
-    const bool tile_major = list || (cob > 1 && wbytes <= 3.0 * 1024 * 1024);   // (list items are always (tile, slab) pairs)
-    a.cob = tile_major ? cob : 0;
-    // the coarse layers' 2-D grid: a slab per XCD when the slabs divide over the eight XCDs, every z-slice starts on XCD 0 and the
-    // weight image outweighs the input maps (they are then what each XCD re-reads; WMD_XCD_SLAB=0/1 forces it off / on)
-    {
-        static const int xs = env_int("WMD_XCD_SLAB", -1);
-        const size_t tiles_n = (size_t)g->B * plan.tiles_x * plan.tiles_y;
-        const double in_bytes = 4.0 * g->B * ((double)g->C1 * H1 * W1 + (double)g->C2 * g->H * g->W);
-        const bool fits = !tile_major && c.TAPS >= 17 && cob % 8 == 0 && (tiles_n * cob) % 8 == 0;
-        a.xcd_slab = fits && (xs >= 0 ? xs != 0 : wbytes > in_bytes) ? 1 : 0;
-    }
-    dim3 grid((unsigned)((size_t)g->B * plan.tiles_x * plan.tiles_y * (tile_major ? cob : 1)), tile_major ? 1u : (unsigned)cob,
-              (unsigned)plan.ksplit);
-    if (env_int("WMD_CONV_VERBOSE", 0))
-        // (sig = the autotuner's problem signature: profiles key the counters of a launch by it, see tools/make_profile_summary.py)
-        fprintf(stderr, "[wmd] conv %dx%d C%d+%d->%d k%d: cfg %s grid %u,%u,%u block %d sig conv|%d|%d|%d|%d|%d|%d|%d|%d%s\n", g->H, g->W, g->C1,
-                g->C2, g->Cout, g->ksize, c.name, grid.x, grid.y, grid.z, c.WM * c.WN * 64, g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout,
-                g->ksize, shift1 ? "|dgrad" : "");
-    const double pix = (double)g->B * g->H * g->W;
-    {
-        // algorithmic work: 2*Cin*k*k*Cout FLOP per output pixel; bytes: inputs + weights + outputs once
-        ProfScope prof(c.name, 2.0 * a.Cin * taps * g->Cout * pix,
-                       4.0 * (pix * g->C1 / (a.up1 * a.up1) + pix * g->C2 + (double)a.Cin * taps * g->Cout + pix * g->Cout),
-                       (hipStream_t)stream);
-        if (c.TAPS == 16) prof.mfma(2.0 * a.Cin * 9 * g->Cout * pix / 2.25);
-        if (c.TAPS >= 17) {   // 32x32x2 MFMAs of 4096 FLOP: per block its tile groups x chunks x K-steps x positions
-            const int n_up = (wino32_pure(a, c.CK) && a.up1 == 2) ? a.C1 / c.CK : 0;
-            const int groups = c.TAPS == 17 ? c.WN / 2 : 1;
-            prof.mfma(4096.0 * grid.x * grid.y * groups * (c.CK / 2) * (9.0 * n_up + 16.0 * (plan.nchunks - n_up)));
-        }
-        c.launch(a, grid, (hipStream_t)stream);
-    }
-    st = check_launch("conv_fwd_kernel");
-    if (st) return st;
-    if (ticket) return st;   // the last K-slice block of every item has written the final values
-    if (list) {
-        if (plan.ksplit > 1) {   // (ksmax = 1: the device can never split, no second pass)
-            const int ntiles = g->B * plan.tiles_x * plan.tiles_y;
-            ProfScope prof("conv_splitk_reduce_list_kernel", 0.0, 0.0, (hipStream_t)stream);
-            hipLaunchKernelGGL(conv_splitk_reduce_list_kernel, dim3(ntiles, (g->Cout + kRedCh - 1) / kRedCh), dim3(256), 0, (hipStream_t)stream, g->workspace, g->bias, g->y,
-                               g->out_tiles, g->out_tile_count, g->out_mask, g->B, g->Cout, g->H, g->W, c.TH, c.TW, plan.tiles_x,
-                               plan.tiles_y, cob, plan.nchunks, plan.ksplit, a.list_slots, g->act, g->slope);
-            st = check_launch("conv_splitk_reduce_list_kernel");
-        }
-        return st;
-    }
-    if (plan.ksplit > 1) {
-        const size_t n = (size_t)g->B * g->Cout * g->H * g->W;
-        const int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
-        ProfScope prof("conv_splitk_reduce_kernel", (double)n * plan.ksplit, 4.0 * n * (plan.ksplit + 1), (hipStream_t)stream);
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g->workspace,
-                           g->bias, g->y, n, (size_t)g->H * g->W, g->Cout, plan.ksplit, g->act, g->slope, g->gate, g->gate_act,
-                           g->gate_slope, g->out_mask);
-        st = check_launch("conv_splitk_reduce_kernel");
-    }
-    return st;
+    fill_args(g, plan, shift1, H1, W1, a);
+    // split-K finished inside the convolution needs a ticket region.  No ring (allocation refused, or the first use would fall inside a
+    // stream capture): the second-stage kernels run as before.
+    if (plan.ticket && plan.ksplit > 1) a.tickets = ticket_region((size_t)g->B * plan.tiles_x * plan.tiles_y * plan.cob, s);
+    if (a.tickets || g->out_tiles) a.y_final = g->y;   // whoever writes the final values of a split launch from inside the convolution
+    const dim3 grid = choose_grid(g, plan, H1, W1, a);
+    const int st = launch_conv(g, plan, a, grid, s);
+    if (st || a.tickets) return st;   // (tickets: the last K-slice block of every item has written the final values)
+    return finish_splitk(g, plan, a, s);
 }

@@ -1,5 +1,5 @@
 // conv_wino32_kernel instantiations: (TH, TW, WN, CK) = pixel tile, tile groups per block (each two waves: the position
-// halves), channels per chunk.  Included by wmd_conv_wino32.hip (explicit instantiation) and by wmd_conv_fwd.hip (table).
+// halves), channels per chunk.  Included by wmd_conv_wino32.hip (explicit instantiation) and by wmd_conv_fwd.hip (configuration table: ConvFamily::Wino32 entries).
 WMD_W32_INST(8, 32, 2, 8)     // co32 x 256px, 4 waves, 54 KB of LDS: two blocks per CU
 WMD_W32_INST(4, 64, 2, 8)     // co32 x 256px, 4 waves; a tile group = one row of 32 tiles (conflict-free patch reads)
 WMD_W32_INST(16, 16, 2, 8)    // co32 x 256px, 4 waves, 16 x 16 tile (80-wide maps)

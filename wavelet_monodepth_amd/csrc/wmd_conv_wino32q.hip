@@ -20,7 +20,7 @@
 //     lane each; the output leaves through whole 128-byte lines like conv_wino32_kernel's (LDS transpose inside the wave).
 // Contract: PURE channel chunking is required (every CK-chunk inside one source tensor; no generic gather).  Masks and work
 // lists ARE supported -- the MASKED and LIST instantiations below serve the block-sparse levels (input mask in the dword gather
-// offsets, tile-activity test, output select; 8x16 list tile with the device-chosen K split) and plan_conv offers TAPS == 18 to
+// offsets, tile-activity test, output select; 8x16 list tile with the device-chosen K split) and plan_conv offers ConvFamily::Wino32Q to
 // in_mask / out_mask / out_tiles launches; the only masked case declined is an upsampled input mask without the 2x2 promise
 // (wmd_conv_args.in_mask_2x2 == 0), which returns WMD_ERR_UNSUPPORTED when forced.
 #include <algorithm>
