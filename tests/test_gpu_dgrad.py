@@ -17,7 +17,8 @@ import pytest
 import torch
 
 from oracle import decoder_ref as R
-from util import bench_tune_cache_name, channel_subset, committed_entries, quarter_family_declines
+from util import (bench_tune_cache_name, channel_subset, chunk_channels, committed_entries, family, offered_splits,
+                  quarter_family_declines, serves, split_accepted)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,43 +34,6 @@ TICKETS = collections.Counter()      # family -> in-kernel split-K finishes amon
 def dev():
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
-
-
-def family(name):
-    if name.startswith("conv_wino32q"):
-        return "wino32q"
-    if name.startswith("conv_wino32"):
-        return "wino32"
-    if name.startswith("conv_wino"):
-        return "wino"
-    return "1x1" if name.endswith(",1>") else "direct3x3"
-
-
-def serves(name, k):
-    """the tuner's candidate filter (tuner.tune): direct kernels of the layer's tap count, every Winograd entry for 3x3"""
-    return name.endswith(",%d>" % (9 if k == 3 else 1)) or (k == 3 and name.startswith("conv_wino"))
-
-
-def chunk_channels(name):
-    """CK of a table entry: the last template argument of the Winograd kernels, the one before TAPS of conv_fwd_kernel"""
-    args = name[name.index("<") + 1:-1].split(",")
-    return int(args[-1] if name.startswith("conv_wino") else args[-2])
-
-
-def split_accepted(name, ks, red):
-    """Must the planner accept a forced split ks of a reduction over `red` channels?  k > 0 needs k chunks; -k (the second-stage
-    sum of a kernel that also finishes in-kernel) exists for the 32x32x2 families only."""
-    nchunks = -(-red // chunk_channels(name))
-    if ks < 0 and not family(name).startswith("wino32"):
-        return False
-    return nchunks >= abs(ks)
-
-
-def offered_splits():
-    """the tuner's whole offer (tuner.tune): k slices (finished in-kernel by the 32x32x2 families, by the second-stage kernel
-    elsewhere) and -k (the second-stage form of a kernel that has both; the planner must refuse it for the others)"""
-    from wavelet_monodepth_amd import tuner
-    return tuple(tuner.KSPLITS) + tuple(-k for k in tuner.KSPLITS if k > 1)
 
 
 def _gen(tag):

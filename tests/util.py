@@ -153,6 +153,43 @@ def quarter_family_declines(name, C1, C2, masked=False, up=1, promise=1):
     return (C1 + C2) % 8 != 0 or (C2 > 0 and C1 % 8 != 0) or (masked and up == 2 and not promise)
 
 
+def family(name):
+    if name.startswith("conv_wino32q"):
+        return "wino32q"
+    if name.startswith("conv_wino32"):
+        return "wino32"
+    if name.startswith("conv_wino"):
+        return "wino"
+    return "1x1" if name.endswith(",1>") else "direct3x3"
+
+
+def serves(name, k):
+    """the tuner's candidate filter (tuner.tune): direct kernels of the layer's tap count, every Winograd entry for 3x3"""
+    return name.endswith(",%d>" % (9 if k == 3 else 1)) or (k == 3 and name.startswith("conv_wino"))
+
+
+def chunk_channels(name):
+    """CK of a table entry: the last template argument of the Winograd kernels, the one before TAPS of conv_fwd_kernel"""
+    args = name[name.index("<") + 1:-1].split(",")
+    return int(args[-1] if name.startswith("conv_wino") else args[-2])
+
+
+def split_accepted(name, ks, red):
+    """Must the planner accept a forced split ks of a reduction over `red` channels?  k > 0 needs k chunks; -k (the second-stage
+    sum of a kernel that also finishes in-kernel) exists for the 32x32x2 families only."""
+    nchunks = -(-red // chunk_channels(name))
+    if ks < 0 and not family(name).startswith("wino32"):
+        return False
+    return nchunks >= abs(ks)
+
+
+def offered_splits():
+    """the tuner's whole offer (tuner.tune): k slices (finished in-kernel by the 32x32x2 families, by the second-stage kernel
+    elsewhere) and -k (the second-stage form of a kernel that has both; the planner must refuse it for the others)"""
+    from wavelet_monodepth_amd import tuner
+    return tuple(tuner.KSPLITS) + tuple(-k for k in tuner.KSPLITS if k > 1)
+
+
 def bench_tune_cache_name():
     """bench.TUNE_CACHE, read without executing bench.py (collection must not start anything); the tests check it against the
     imported module"""
