@@ -32,11 +32,12 @@ def compute_reprojection_loss(pred, target, use_ssim=True):
 
 def backproject(depth, inv_K):
     B, _, H, W = depth.shape
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
-    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W)], 0).unsqueeze(0).repeat(B, 1, 1)
+    dt = depth.dtype   # the pixel grid and the homogeneous ones follow the depth map: float64 in, float64 throughout
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=dt)], 0).unsqueeze(0).repeat(B, 1, 1)
     cam = torch.matmul(inv_K[:, :3, :3], pix)
     cam = depth.view(B, 1, -1) * cam
-    return torch.cat([cam, torch.ones(B, 1, H * W)], 1)
+    return torch.cat([cam, torch.ones(B, 1, H * W, dtype=dt)], 1)
 
 
 def project(points, K, T, H, W, eps=1e-7):
@@ -109,13 +110,13 @@ def compute_losses(inputs, outputs, opt):
             ident_l, reproj_l = torch.min(ident, 1, keepdim=True)[0], torch.min(reproj, 1, keepdim=True)[0]
         parts = [reproj_l, ident_l] + ([dh_reproj] if dh_reproj is not None else [])
         idxs = torch.argmin(torch.cat(parts, 1), 1, keepdim=True)
-        mask = (idxs != 1).float()
+        mask = (idxs != 1).to(reproj_l.dtype)
         r = (reproj_l * mask).sum() / (mask.sum() + 1e-7)
         losses["reproj_loss/{}".format(scale)] = r
         outputs["identity_selection/{}".format(scale)] = 1 - mask
         dhl = 0
         if opt.use_depth_hints:
-            dmask = (idxs == 2).float()
+            dmask = (idxs == 2).to(reproj_l.dtype)
             dh = torch.log(torch.abs(inputs["depth_hint"] - outputs[("depth", 0, scale)]) + 1) * inputs["depth_hint_mask"]
             dhl = (dh * dmask).sum() / (dmask.sum() + 1e-7)
             losses["depth_hint_loss/{}".format(scale)] = dhl
@@ -123,5 +124,5 @@ def compute_losses(inputs, outputs, opt):
         loss = r + dhl + opt.disparity_smoothness * get_smooth_loss(norm_disp, color) / (2 ** scale)
         total = total + loss
         losses["loss/{}".format(scale)] = loss
-    losses["loss"] = total / len(opt.loss_scales)
+    losses["loss"] = total / len(getattr(opt, "scales", opt.loss_scales))   # num_scales = len(opt.scales), trainer.py:47,557
     return losses

@@ -119,6 +119,162 @@ def loss_case(B=2, H=32, W=64, seed=17, hints=False):
     return inputs, outputs
 
 
+def scaled_intrinsics(B, H, W):
+    """KITTI-like K and inv_K [B,4,4] for an H x W frame (the intrinsics of photo_case)"""
+    K = np.tile(np.array([[0.58 * W, 0, 0.5 * W, 0], [0, 1.92 * H, 0.5 * H, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float32), (B, 1, 1))
+    return K, np.linalg.inv(K).astype(np.float32)
+
+
+def box3(a):
+    """3x3 box blur with edge padding, in place (the smoothing of photo_case)."""
+    H, W = a.shape[-2:]
+    pad = np.pad(a, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge")
+    a[:] = sum(pad[:, :, i:i + H, j:j + W] for i in range(3) for j in range(3)) / np.float32(9)
+    return a
+
+
+WARP_MARGIN = 1e-3   # px: a sample this close to an integer or to a clamp edge is excluded from the gradient comparison
+
+
+def warp_edge_case(B, C, H, W, Hs, Ws, seed):
+    """Inputs of warp_frame for a [B,C,Hs,Ws] source sampled into a [B,1,H,W] target: intrinsics scaled to the target size, a
+    small pose (a yaw of 0.02 (b+1) rad, a translation of (0.3 (b+1), -0.05, -0.2): the camera backs off, so samples leave
+    over all four borders), depths in 2-30 (uniform in the disparity, like a street scene).  Also the float64 sample
+    coordinates (ux, uy) [B,H,W] in source pixels, and `excl` [B,H,W]: ux or uy within WARP_MARGIN of an integer (the bilinear
+    cell changes there and d out / d coord jumps) or of a clamp edge 0 / size-1 (the clip multiplier jumps between 0 and 1).
+    `gout` [B,C,H,W] is the upstream gradient, zero at excluded pixels, so that neither ddepth there nor the dT sum depends
+    on which side of the jump a rounding lands.  `clamped` is the share of the 2*B*H*W coordinates on the border clamp."""
+    src = box3(synth.uniform((B, C, Hs, Ws), "we_src", seed, 0.0, 1.0).astype(np.float32))
+    disp = synth.uniform((B, 1, H, W), "we_disp", seed, 1.0 / 30.0, 0.5).astype(np.float32)
+    depth = np.clip(1.0 / disp.astype(np.float64), 2.0, 30.0).astype(np.float32)
+    K, inv_K = scaled_intrinsics(B, H, W)
+    T = np.tile(np.eye(4, dtype=np.float32), (B, 1, 1))
+    for b in range(B):
+        ang = 0.02 * (b + 1)
+        T[b, :3, :3] = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]], np.float32)
+        T[b, :3, 3] = [0.3 * (b + 1), -0.05, -0.2]
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    pix = np.stack([xs.reshape(-1), ys.reshape(-1), np.ones(H * W)], 0)
+    cam = depth.astype(np.float64).reshape(B, 1, -1) * (inv_K.astype(np.float64)[:, :3, :3] @ pix)
+    cam = np.concatenate([cam, np.ones((B, 1, H * W))], 1)
+    c = (K.astype(np.float64) @ T.astype(np.float64))[:, :3, :] @ cam
+    ux = (c[:, 0] / (c[:, 2] + 1e-7)).reshape(B, H, W) * Ws / (W - 1) - 0.5
+    uy = (c[:, 1] / (c[:, 2] + 1e-7)).reshape(B, H, W) * Hs / (H - 1) - 0.5
+    near = lambda u: np.abs(u - np.rint(u)) < WARP_MARGIN      # the clamp edges 0 and size-1 are integers themselves
+    excl = near(ux) | near(uy)
+    clamped = lambda u, n: (u <= 0) | (u >= n - 1)
+    gout = synth.uniform((B, C, H, W), "we_g", seed, 0.0, 1.0).astype(np.float32) * ~excl[:, None]
+    return dict(src=src, depth=depth, K=K, inv_K=inv_K, T=T, ux=ux, uy=uy, excl=excl, gout=gout,
+                clamped=float((clamped(ux, Ws).mean() + clamped(uy, Hs).mean()) / 2))
+
+
+def smooth_tie_case(B, C, H, W, seed):
+    """disp [B,1,H,W] in 0.05-0.9 and img [B,C,H,W] for get_smooth_loss, with the two places where |a - b| is delicate:
+    constant 3x3 patches (clipped to H x (W-1) on tiny maps, so that the map never goes constant), whose inner pairs are
+    exact ties (sgn(0) == 0: no gradient from either side), and neighbours one ulp apart (the sign must survive)."""
+    disp = synth.uniform((B, 1, H, W), "st_disp", seed, 0.05, 0.9).astype(np.float32)
+    img = synth.uniform((B, C, H, W), "st_img", seed, 0.0, 1.0).astype(np.float32)
+    g = np.random.default_rng(zlib.crc32(b"smooth_tie") + seed)
+    ph, pw = min(3, H), min(3, W - 1)
+    n = max(1, B * H * W // 128)
+    for b, y, x in zip(g.integers(0, B, n), g.integers(0, H - ph + 1, n), g.integers(0, W - pw + 1, n)):
+        disp[b, 0, y:y + ph, x:x + pw] = disp[b, 0, y, x]
+    for b, y, x in zip(g.integers(0, B, n), g.integers(0, H, n), g.integers(0, W - 1, n)):
+        disp[b, 0, y, x + 1] = np.nextafter(disp[b, 0, y, x], np.float32(1 if (x + y) & 1 else 0))
+    return disp, img
+
+
+def fully_tied(disp):
+    """[B,1,H,W] mask of the pixels all of whose neighbour pairs (left, right, up, down, where they exist) are exact ties"""
+    d = disp[:, 0]
+    m = np.ones(d.shape, bool)
+    ex, ey = d[:, :, :-1] == d[:, :, 1:], d[:, :-1, :] == d[:, 1:, :]
+    m[:, :, :-1] &= ex
+    m[:, :, 1:] &= ex
+    m[:, :-1, :] &= ey
+    m[:, 1:, :] &= ey
+    return m[:, None]
+
+
+SSIM_L1_MARGIN = 1e-6   # |x - y| below this: d|x - y| jumps; excluded from the gradient comparison
+
+
+def ssim_edge_case(B, C, H, W, seed, smoothed):
+    """Two frames in [0, 1) for SSIM / compute_reprojection_loss: 3x3-smoothed (E[x^2] - mu^2 cancels: the hard numerical
+    case) or iid (where L1 ties essentially cannot occur); upstream gradients `w` [B,C,H,W] (mode 0) and `w1` [B,1,H,W]
+    (mode 1); `excl` [B,C,H,W] marks |x - y| < SSIM_L1_MARGIN."""
+    x = synth.uniform((B, C, H, W), "se_x", seed, 0.0, 1.0).astype(np.float32)
+    y = synth.uniform((B, C, H, W), "se_y", seed, 0.0, 1.0).astype(np.float32)
+    if smoothed:
+        box3(x), box3(y)
+    w = synth.uniform((B, C, H, W), "se_w", seed, 0.0, 1.0).astype(np.float32)
+    w1 = synth.uniform((B, 1, H, W), "se_w1", seed, 0.0, 1.0).astype(np.float32)
+    excl = np.abs(x.astype(np.float64) - y.astype(np.float64)) < SSIM_L1_MARGIN
+    return dict(x=x, y=y, w=w, w1=w1, excl=excl)
+
+
+# ---- the photometric oracle (oracle/photo_ref.py) at a chosen precision; every result comes back as float64 numpy -------
+
+def _td(a, dtype, g=False):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).requires_grad_(g)
+
+
+def _n64(v):
+    return v.detach().double().numpy()
+
+
+def oracle_warp(case, dtype):
+    """-> (out, ddepth, dT) of oracle.photo_ref.warp_frame with the upstream gradient case["gout"]"""
+    from oracle import photo_ref as P
+    d, T = _td(case["depth"], dtype, True), _td(case["T"], dtype, True)
+    out = P.warp_frame(_td(case["src"], dtype), d, _td(case["K"], dtype), _td(case["inv_K"], dtype), T)
+    (out * _td(case["gout"], dtype)).sum().backward()
+    return _n64(out), _n64(d.grad), _n64(T.grad)
+
+
+def oracle_ssim(case, mode, dtype):
+    """mode "ssim": the SSIM module; "reproj" / "l1": compute_reprojection_loss with / without SSIM -> (out, dx, dy)"""
+    from oracle import photo_ref as P
+    x, y = _td(case["x"], dtype, True), _td(case["y"], dtype, True)
+    out = P.ssim(x, y) if mode == "ssim" else P.compute_reprojection_loss(x, y, mode == "reproj")
+    (out * _td(case["w" if mode == "ssim" else "w1"], dtype)).sum().backward()
+    return _n64(out), _n64(x.grad), _n64(y.grad)
+
+
+SMOOTH_UPSTREAM = 0.37   # d(loss)/d(smoothness) handed to the backward: not 1, so that a dropped factor shows
+
+
+def oracle_smooth(disp, img, dtype):
+    """-> (value, ddisp) of get_smooth_loss, backward from SMOOTH_UPSTREAM * value"""
+    from oracle import photo_ref as P
+    d = _td(disp, dtype, True)
+    sm = P.get_smooth_loss(d, _td(img, dtype))
+    (sm * SMOOTH_UPSTREAM).backward()
+    return _n64(sm), _n64(d.grad)
+
+
+def edge_err(a, ref64, keep=None):
+    """max |a - ref64| over the kept entries, relative to max |ref64| (absolute where the reference is all zero)"""
+    a, ref64 = np.asarray(a, np.float64), np.asarray(ref64, np.float64)
+    diff = np.abs(a - ref64)
+    if keep is not None:
+        diff = diff[np.broadcast_to(keep, diff.shape)]
+    scale = float(np.abs(ref64).max()) if ref64.size else 0.0
+    return float(diff.max()) / (scale if scale > 0 else 1.0) if diff.size else 0.0
+
+
+# (B, C, H, W, Hs, Ws) of tests/test_gpu_photo_edges.py: general shapes, source sizes, then the reduce edges of
+# warp_bwd_kernel -> warp_bwd_finish_kernel (nblk = ceil(H W / 1024) capped at 256)
+WARP_CASES = [(2, 3, 5, 7, 5, 7), (3, 1, 17, 33, 17, 33), (2, 3, 16, 24, 8, 12), (2, 3, 12, 20, 24, 40),
+              (1, 3, 32, 32, 32, 32), (2, 3, 25, 41, 25, 41), (1, 3, 256, 256, 256, 256), (1, 3, 257, 256, 257, 256),
+              (1, 3, 513, 512, 513, 512)]
+WARP_DEGENERATE = [(1, 3, 2, 2, 2, 2), (1, 3, 16, 24, 1, 1)]
+# (B, C, H, W): nblk = ceil(B H W / 2048) capped at 512
+SMOOTH_CASES = [(1, 1, 2, 2), (2, 3, 5, 7), (1, 3, 32, 64), (1, 3, 3, 683), (1, 3, 257, 512), (1, 1, 1025, 1024)]
+SSIM_SMALL = [(1, 3, 2, 2), (1, 1, 2, 9), (2, 3, 3, 2), (2, 3, 5, 7), (1, 3, 17, 33)]
+SSIM_WRAP = [((1, 3, 700, 1000), "ssim"), ((1, 1, 1025, 2050), "reproj")]   # n > 8192 * 256: the grid-stride loop runs twice
+
+
 def check_packed(out, gold, tol, exact=True, limit=4096):
     """Compare a decoder output dict with a PACKED full-size fixture (tests/golden/make_golden.py::pack_outputs): float
     maps as strided samples ("s|key"), boolean masks bit-packed ("m|key" + "mshape|key"), integers ("i|key")."""
