@@ -2,7 +2,7 @@
 
 wmd_conv_wgrad runs one of three families, each over a split of the pixel tiles into partial sums that a second kernel reduces in
 a fixed order: the Winograd F(2x2,3x3) table (conv_wgrad_wino_kernel / conv_wgrad_wino32_kernel, tune_cfg = k forces entry k-1;
-wgrad_wino_reduce_kernel), the direct MFMA table kWCfgs of wmd_conv_bwd.hip (3x3 and 1x1; tune_cfg = -1, WMD_WGRAD_CFG=<1-based
+wgrad_wino_reduce_kernel), the direct MFMA table kWCfgs of wmd_conv_wgrad.hip (3x3 and 1x1; tune_cfg = -1, WMD_WGRAD_CFG=<1-based
 index> forces an entry; wgrad_reduce_kernel) and the VALU kernel of the heads' Cout <= 4 filters (WMD_WGRAD_SMALLCO=1).  Every
 (entry, split) pair is compared here, every launch into NaN-filled dw / db over a NaN-filled workspace; the split the plan used is
 read back from the workspace it asked for, and the kernel that ran from the library's launch profile.
@@ -61,8 +61,8 @@ def wino_names():
 
 
 def direct_names():
-    """kWCfgs in table order (WMD_WGRAD_CFG counts from 1), read from wmd_conv_bwd.hip: the C ABI does not list this table"""
-    src = open(os.path.join(ROOT, "wavelet_monodepth_amd", "csrc", "wmd_conv_bwd.hip")).read()
+    """kWCfgs in table order (WMD_WGRAD_CFG counts from 1), read from wmd_conv_wgrad.hip: the C ABI does not list this table"""
+    src = open(os.path.join(ROOT, "wavelet_monodepth_amd", "csrc", "wmd_conv_wgrad.hip")).read()
     body = src[src.index("static const WgradCfg kWCfgs[] = {"):]
     body = body[:body.index("};")]
     rows = re.findall(r"^\s*WMD_WCFG\(([^)]*)\)", body, flags=re.M)

@@ -814,6 +814,49 @@ def test_conv_planner_workspace_answers_are_pinned(what, fields, expected, monke
     assert _lib.lib().wmd_conv_fwd_workspace_floats(C.byref(a)) == expected, what
 
 
+# (what the case is, (B, H, W, C1, up1, C2, Cout, ksize), further wmd_conv_wgrad_args fields -- a tune_cfg given as a string is
+#  counted from wmd_conv_wgrad_num_configs() --, switches set, wmd_conv_wgrad_workspace_floats as recorded from the library before
+#  the weight gradient got one configuration type, one plan and one launch path)
+_WGRAD_L1 = (12, 12, 40, 256, 2, 256, 256, 3)
+_WGRAD_PLANNER_PINS = [
+    ("finest layer: 32x32x2 Winograd", (12, 96, 320, 32, 2, 64, 32, 3), {}, {}, 12591104),
+    ("coarsest layer", (12, 6, 20, 512, 1, 0, 256, 3), {}, {}, 16779264),
+    ("coarse layer with concat", _WGRAD_L1, {}, {}, 16779264),
+    ("coarse layer, direct kernel asked for", _WGRAD_L1, dict(tune_cfg=-1), {}, 4719616),
+    ("coarse layer, first Winograd entry", _WGRAD_L1, dict(tune_cfg=1), {}, 8389632),
+    ("coarse layer, last Winograd entry", _WGRAD_L1, dict(tune_cfg="n"), {}, 16779264),
+    ("coarse layer, 7 slices", _WGRAD_L1, dict(tune_nsplit=7), {}, 14681856),
+    ("coarse layer, a split clamped to the pixel tiles", _WGRAD_L1, dict(tune_nsplit=10**6), {}, 151013376),
+    ("coarse layer, Winograd switched off", _WGRAD_L1, {}, {"WMD_WGRAD_WINO": "0"}, 4719616),
+    ("a head's Cout = 3 filter on 16-row tiles", (1, 16, 48, 64, 1, 0, 3, 3), {}, {}, 12300),
+    ("2 x 2 map: one tile", (3, 2, 2, 8, 1, 0, 16, 3), {}, {}, 1168),
+    ("1x1 layer: flattened pixels", (12, 96, 320, 32, 1, 0, 32, 1), {}, {}, 270336),
+    ("VALU small-Cout kernel", (2, 37, 300, 6, 1, 0, 3, 3), {}, {"WMD_WGRAD_SMALLCO": "1"}, 1320),
+    ("refused: table index past the end", _WGRAD_L1, dict(tune_cfg="n+1"), {}, 0),
+    ("refused: a Winograd entry for a 1x1 filter", (12, 96, 320, 32, 1, 0, 32, 1), dict(tune_cfg=1), {}, 0),
+]
+
+
+@pytest.mark.parametrize("what,shape,fields,env,expected", _WGRAD_PLANNER_PINS, ids=[p[0] for p in _WGRAD_PLANNER_PINS])
+def test_wgrad_planner_workspace_answers_are_pinned(what, shape, fields, env, expected, monkeypatch):
+    """The weight gradient's plan is host code: its choice of entry and pixel split shows in wmd_conv_wgrad_workspace_floats
+    (nsplit * the family's slice) without a GPU.  The six switches are cleared unless the case sets one."""
+    import ctypes as C
+    from wavelet_monodepth_amd import _lib
+    for name in ("WMD_WGRAD_CFG", "WMD_WGRAD_NSPLIT", "WMD_WGRAD_WINO", "WMD_WGRAD_WINO_CFG", "WMD_WGRAD_SMALLCO", "WMD_WGRAD_NSPLIT_CAP"):
+        monkeypatch.delenv(name, raising=False)
+    for name, v in env.items():
+        monkeypatch.setenv(name, v)
+    l = _lib.lib()
+    n = l.wmd_conv_wgrad_num_configs()
+    B, H, W, C1, up1, C2, Cout, ksize = shape
+    a = _lib.ConvWgradArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=Cout, ksize=ksize, pad_mode=1, x1=1, x2=1 if C2 else None, dz=1,
+                           dw=1, dbias=1, workspace=None, workspace_floats=0, tune_cfg=0, tune_nsplit=0)
+    for k, v in fields.items():
+        setattr(a, k, {"n": n, "n+1": n + 1}.get(v, v))
+    assert l.wmd_conv_wgrad_workspace_floats(C.byref(a)) == expected, what
+
+
 def test_bind_inputs_routes_are_decided_on_the_host():
     """decoder._bound (round 6): the route of a graph-mode forward is host logic -- buffers themselves / a recurring address set /
     copy -- and is decided before anything is launched.  Checked on stand-in tensors that record their copies (no GPU here)."""

@@ -413,7 +413,7 @@ constexpr bool wino32_has_list(int TH, int TW, int WN, int CK) {
     return CK == 8 && ((TH == 8 && TW == 16 && WN == 1) || (TH == 16 && TW == 16 && WN == 2));
 }
 
-// weight-gradient kernels (wmd_conv_bwd.hip, wmd_conv_wgrad32.hip)
+// weight-gradient kernels (wmd_conv_wgrad.hip, wmd_conv_wgrad32.hip)
 struct WgradKArgs {
     const float* x1;
     const float* x2;
@@ -428,5 +428,11 @@ struct WgradKArgs {
 // conv_wgrad_wino32_kernel (wmd_conv_wgrad32.hip): block = WCO x WCI slabs of 32 out / 32 in channels, two position halves each
 template <int TH, int TW, int WCO, int WCI>
 void launch_wgrad_wino32(const WgradKArgs& a, dim3 grid, hipStream_t s);
+
+// wmd_conv_bwd.hip: the shape checks every backward entry point shares, and conv_dgrad_fold_kernel (the adjoint of pad + concat +
+// upsample on a padded-domain gradient g) as the data gradient and the depthwise backward launch it
+int validate_bwd(int B, int H, int W, int C1, int up1, int C2, int Cout, int ksize, int pad_mode, const char* who);
+void launch_dgrad_fold(const float* g, float* dx1, float* dx2, int B, int C1, int C2, int H, int W, int up1, int pad_mode, int halo,
+                       const float* x1_fwd, int x1_act, float x1_slope, hipStream_t s);
 
 }  // namespace wmd

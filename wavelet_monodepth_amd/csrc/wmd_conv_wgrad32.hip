@@ -1,6 +1,6 @@
 // Winograd F(2x2,3x3) weight gradient on v_mfma_f32_32x32x2_f32 (gfx950).
 //
-// Same operator as conv_wgrad_wino_kernel (wmd_conv_bwd.hip): autograd of ConvBlock / Conv3x3 + upsample + concat + pad with
+// Same operator as conv_wgrad_wino_kernel (wmd_conv_wgrad.hip): autograd of ConvBlock / Conv3x3 + upsample + concat + pad with
 // respect to the filter (the reference gets it from torch.autograd, KITTI/trainer.py:211, NYUv2/train.py:327),
 //     dU_xi[co, ci] = sum_tiles dM_xi[tile, co] * V_xi[tile, ci],   dM = A dY A^T,   V = B^T d B,   dg = G^T dU G,
 // same partial layout ([split][16][Cout*Cin] + bias sums; wgrad_wino_reduce_kernel finishes it), same LDS-DMA gather of dz
