@@ -252,15 +252,18 @@ def test_sparse_decoder_full_density_vs_reference_golden(dev, thr):
     _check(out, gold)
 
 
-@pytest.mark.parametrize("tiles", ["0", "1"], ids=["gather", "tiles"])
+@pytest.mark.parametrize("tiles", [{"WMD_SPARSE_TILES": "0"}, {"WMD_SPARSE_TILES": "1"}, {"WMD_SPARSE_LISTS": "0"}],
+                         ids=["gather", "tiles", "tiles_no_lists"])
 @pytest.mark.parametrize("name,hw,seed,thr", [("64x64", (64, 64), 1, 0.05), ("64x64", (64, 64), 1, 0.1),
                                               ("96x160", (96, 160), 2, 0.15), ("96x160", (96, 160), 2, 0.2)])
 def test_sparse_decoder_vs_reference_golden_with_reference_masks(dev, name, hw, seed, thr, tiles, monkeypatch):
     """Feed the reference's own threshold masks (a pixel sitting exactly at the threshold may legitimately
     flip with fp32 rounding); everything downstream — dilations, compaction, gather-GEMMs, heads, IDWT, the five
-    mask families and the integer op model — must then match the reference exactly / to 1e-4.  Both forms of the sparse
-    levels: gather-GEMMs over the pixel lists, and the block-sparse dense kernels + masked fused heads."""
-    monkeypatch.setenv("WMD_SPARSE_TILES", tiles)
+    mask families and the integer op model — must then match the reference exactly / to 1e-4.  Every form of the sparse
+    levels: gather-GEMMs over the pixel lists, the block-sparse dense kernels + masked fused heads in their default (work-list)
+    form, and their tile form (WMD_SPARSE_LISTS=0: per-forward pool, the counts accumulated by the mask launch)."""
+    for k, v in tiles.items():
+        monkeypatch.setenv(k, v)
     gold = load_golden("kitti_sparse_r18_%s_thr%g.npz" % (name, thr))
     feats = kitti_feats(2 if name == "64x64" else 1, hw[0], hw[1], seed=seed)
     force = {i: t(gold["wavelet_mask|%d" % (i - 1)])[0, 0, ::2, ::2] for i in (3, 2, 1)}
@@ -281,8 +284,13 @@ def test_sparse_decoder_empty_masks_vs_reference_golden(dev):
     _check(out, gold)
 
 
+@pytest.mark.parametrize("form", [{}, {"WMD_SPARSE_LISTS": "0"}, {"WMD_SPARSE_LISTS": "0", "WMD_SPARSE_UNFUSED_MASKS": "1"},
+                                  {"WMD_SPARSE_TILES": "0"}], ids=["default", "tiles_no_lists", "tiles_unfused_masks", "gather"])
 @pytest.mark.parametrize("name,hw,seed,thr", [("64x64", (64, 64), 1, 0.1), ("96x160", (96, 160), 2, 0.15)])
-def test_sparse_decoder_free_running_masks(dev, name, hw, seed, thr):
+def test_sparse_decoder_free_running_masks(dev, name, hw, seed, thr, form, monkeypatch):
+    """The decoder's own thresholds in every form of the sparse levels and both forms of the mask launch."""
+    for k, v in form.items():
+        monkeypatch.setenv(k, v)
     gold = load_golden("kitti_sparse_r18_%s_thr%g.npz" % (name, thr))
     feats = kitti_feats(2 if name == "64x64" else 1, hw[0], hw[1], seed=seed)
     out = _decoder(dev)([f[:1].to(dev) for f in feats], thr)

@@ -769,7 +769,7 @@ def test_bench_dump_outputs_names_the_maps_and_keeps_the_size_bound(tmp_path):
 
 
 def test_list_tile_query_agrees_with_the_planner_table():
-    """wmd_conv_list_tile_supported (what sparse_decoder.tile_for asks) and plan_conv's work-list filter are ONE
+    """wmd_conv_list_tile_supported (what sparse_decoder._list_tile asks) and plan_conv's work-list filter are ONE
     predicate now; the two shapes with LIST instantiations must be reported, others not."""
     from wavelet_monodepth_amd import _lib
     l = _lib.lib()
