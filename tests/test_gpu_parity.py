@@ -732,6 +732,33 @@ def test_fused_head_level_vs_oracle(dev, C, H, W):
     assert_close(disp, torch.clamp(out_ref / 2 ** (s - 1), 0, 1), 2e-6, "disp")
 
 
+@pytest.mark.parametrize("B,H,W", [(2, 3, 5), (1, 5, 7)])
+def test_low_pass_chain_beside_the_fuse_form_vs_oracle(dev, B, H, W):
+    """C = 256 on planes that are not a multiple of 4 pixels: the chained kernel declines the level, so wmd_head_fused_fwd runs the
+    +- heads AND the low-pass chain (a launch of its own, planes 54..62 of the 81-plane buffer) on the FUSE instantiations of
+    conv_fwd_kernel; the shift-sum completes both.  Every output against the oracle, the low-pass plane against the oracle's own
+    chain scale_ll * sigmoid(conv3x3(leaky(conv1x1)))."""
+    from wavelet_monodepth_amd import ops
+    C, s, scale_ll = 256, 4, 16.0
+    x = t(synth.normal((B, C, H, W), "lx", 41))
+    hp = [t(a) for a in synth.conv_params("l1p", C, C, 1, 41)] + [t(a) for a in synth.conv_params("l3p", 3, C, 3, 41)]
+    hn = [t(a) for a in synth.conv_params("l1n", C, C, 1, 41)] + [t(a) for a in synth.conv_params("l3n", 3, C, 3, 41)]
+    hl = [t(a) for a in synth.conv_params("l1l", C // 4, C, 1, 41)] + [t(a) for a in synth.conv_params("l3l", 1, C // 4, 3, 41)]
+    lk = lambda v: torch.nn.functional.leaky_relu(v, 0.1)
+    sp = torch.sigmoid(R.conv3x3(lk(R.conv1x1(x, hp[0], hp[1])), hp[2], hp[3], "reflect"))
+    sn = torch.sigmoid(R.conv3x3(lk(R.conv1x1(x, hn[0], hn[1])), hn[2], hn[3], "reflect"))
+    yh_ref = (2 ** (s - 1) * sp - 2 ** (s - 1) * sn).unsqueeze(1)
+    yl_ref = scale_ll * torch.sigmoid(R.conv3x3(lk(R.conv1x1(x, hl[0], hl[1])), hl[2], hl[3], "reflect"))
+    out_ref = R.haar_idwt(yl_ref, yh_ref)
+    g = lambda v: v.to(dev)
+    yh, out, disp, yl_ll = ops.head_fused_level_nograd(g(x), [g(v) for v in hp], [g(v) for v in hn], scale=2.0 ** (s - 1), yl=None,
+                                                       disp_scale=1.0 / 2 ** (s - 1), clamp01=True, head_ll=[g(v) for v in hl], scale_ll=scale_ll)
+    assert float((yh.cpu() - yh_ref).abs().max()) < 4e-6          # differences of sigmoids: absolute tolerance
+    assert_close(out, out_ref, 2e-6, "idwt")
+    assert_close(disp, torch.clamp(out_ref / 2 ** (s - 1), 0, 1), 2e-6, "disp")
+    assert_close(yl_ll, yl_ref, 2e-6, "low-pass head")
+
+
 @pytest.mark.parametrize("B,H,W", [(2, 160, 320), (3, 131, 270), (1, 322, 320), (7, 96, 160)])
 def test_streaming_head_level_vs_oracle(dev, B, H, W):
     """Round 6: head_stream_kernel (wmd_head_stream.hip) takes wmd_head_level_fwd's plain inference launches from 100 000

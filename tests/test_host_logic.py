@@ -857,6 +857,54 @@ def test_wgrad_planner_workspace_answers_are_pinned(what, shape, fields, env, ex
     assert l.wmd_conv_wgrad_workspace_floats(C.byref(a)) == expected, what
 
 
+# The head front end's host decisions, as recorded from the library before its switches moved into head_switches and its entry
+# points into wmd_head_chain.hip.  (C, B, H, W) -> wmd_head_level_pyramid_supported: 0 = no, 1 = runs, 2 = runs and pays.  The grid
+# crosses the rules: sizes below 8 or not multiples of 8, an empty batch, C = 64, and the "pays" boundary (320 / 328 rows, batch 1 / 8).
+_HEAD_PYRAMID_PINS = {
+    (32, 1, 8, 8): 1, (32, 1, 12, 40): 0, (32, 1, 16, 16): 1, (32, 1, 96, 320): 1, (32, 1, 160, 512): 1, (32, 1, 320, 1024): 2, (32, 1, 328, 1024): 1,
+    (32, 8, 8, 8): 1, (32, 8, 12, 40): 0, (32, 8, 16, 16): 1, (32, 8, 96, 320): 2, (32, 8, 160, 512): 1, (32, 8, 320, 1024): 1, (32, 8, 328, 1024): 1,
+    (32, 12, 8, 8): 1, (32, 12, 12, 40): 0, (32, 12, 16, 16): 1, (32, 12, 96, 320): 2, (32, 12, 160, 512): 2, (32, 12, 320, 1024): 1, (32, 12, 328, 1024): 1,
+    (32, 1, 4, 8): 0, (32, 1, 8, 4): 0, (32, 1, 100, 320): 0, (32, 1, 96, 324): 0, (32, 0, 96, 320): 0, (64, 12, 96, 320): 0, (64, 1, 8, 8): 0,
+}
+# (B, H, W, C, Cout) -> wmd_head3x3_workspace_floats = csplit * B * 2 * Cout * H * W of head_plan, 0 for an unsplit plan
+_HEAD3X3_WORKSPACE_PINS = {
+    (1, 2, 2, 16, 1): 0, (12, 2, 2, 256, 3): 4608, (1, 6, 20, 256, 3): 11520, (12, 6, 20, 256, 3): 138240, (12, 12, 40, 256, 1): 184320,
+    (1, 24, 80, 64, 3): 46080, (12, 24, 80, 64, 3): 552960, (1, 48, 160, 32, 3): 92160, (12, 48, 160, 32, 1): 368640,
+    (1, 96, 320, 16, 3): 0, (12, 96, 320, 16, 1): 0, (1, 96, 320, 32, 3): 368640,
+}
+_HEAD_SWITCH_NAMES = ("WMD_HEAD_CHAIN", "WMD_HEAD_CHAIN_MULTI", "WMD_HEAD_CHAIN_PG256", "WMD_HEAD_STREAM", "WMD_HEAD_STREAM_TH", "WMD_HEAD_STREAM_MIN_PIXELS",
+                      "WMD_SHIFTSUM_CHAIN_SQUARE", "WMD_HEAD_CSPLIT", "WMD_HEAD_NG", "WMD_HEAD_BWD_FUSED")
+_HEAD_PIN_CHILD = """
+import ctypes as C, json, sys
+from wavelet_monodepth_amd import _lib
+l = _lib.lib()
+pyr = [l.wmd_head_level_pyramid_supported(*k) for k in json.loads(sys.argv[1])]
+ws = []
+for B, H, W, Cc, Cout in json.loads(sys.argv[2]):
+    a = _lib.HeadArgs(B=B, H=H, W=W, C=Cc, Cout=Cout, pad_mode=1, mode=2, scale=1.0, xp=1, wgt_p=1, xn=1, wgt_n=1, y=1)
+    ws.append(l.wmd_head3x3_workspace_floats(C.byref(a)))
+print(json.dumps([pyr, ws]))
+"""
+
+
+def test_head_front_end_answers_are_pinned():
+    """The heads' forward decides on the host which level the pyramid launch takes and how head3x3_kernel splits its channels; both
+    show without a GPU.  The switches are read once per process (head_switches), so the library answers in a child process whose
+    environment has none of them set."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in _HEAD_SWITCH_NAMES}
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    out = subprocess.run([sys.executable, "-c", _HEAD_PIN_CHILD, json.dumps(list(_HEAD_PYRAMID_PINS)), json.dumps(list(_HEAD3X3_WORKSPACE_PINS))],
+                         env=env, capture_output=True, text=True, check=True).stdout
+    pyr, ws = json.loads(out)
+    assert dict(zip(_HEAD_PYRAMID_PINS, pyr)) == _HEAD_PYRAMID_PINS
+    assert dict(zip(_HEAD3X3_WORKSPACE_PINS, ws)) == _HEAD3X3_WORKSPACE_PINS
+
+
 def test_bind_inputs_routes_are_decided_on_the_host():
     """decoder._bound (round 6): the route of a graph-mode forward is host logic -- buffers themselves / a recurring address set /
     copy -- and is decided before anything is launched.  Checked on stand-in tensors that record their copies (no GPU here)."""

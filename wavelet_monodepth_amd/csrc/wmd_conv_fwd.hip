@@ -1074,116 +1074,66 @@ static bool plan_conv(const wmd_conv_args* g, ConvPlan* plan, bool have_ws, size
     return found;
 }
 
-}  // namespace wmd
-
-using namespace wmd;
-
-extern "C" int wmd_head_fused_multi_fwd(const wmd_head_fused_args* levels, int n_levels, void* stream) {
-    if (!levels || n_levels < 1 || n_levels > 3) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_multi_fwd: 1..3 levels (got %d)", n_levels);
-    for (int k = 0; k < n_levels; ++k) {
-        const wmd_head_fused_args* g = &levels[k];
-        if (!g->x || !g->wp1 || !g->wp2 || !g->t) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_multi_fwd: level %d: null tensor pointer", k);
-        if (g->B <= 0 || g->H <= 0 || g->W <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_fused_multi_fwd: level %d: B=%d H=%d W=%d", k, g->B, g->H, g->W);
-    }
-    if (head_chain_multi_launch(levels, n_levels, (hipStream_t)stream)) return check_launch("head_chain_multi_kernel");
-    for (int k = 0; k < n_levels; ++k) {      // a level the merged launch cannot take: the per-level launches, same planes
-        const int st = wmd_head_fused_fwd(&levels[k], stream);
-        if (st) return st;
-    }
-    return WMD_OK;
-}
-
-extern "C" int wmd_head_fused_fwd(const wmd_head_fused_args* g, void* stream) {
-    if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: null args");
-    if (!g->x || !g->wp1 || !g->wp2 || !g->t) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: null tensor pointer");
-    if (g->B <= 0 || g->H <= 0 || g->W <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_fused_fwd: B=%d H=%d W=%d", g->B, g->H, g->W);
-    if (g->C != 32 && g->C != 64 && g->C != 128 && g->C != 256)
-        return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: C=%d (32, 64, 128 or 256; other widths run unfused)", g->C);
-    if (g->chain != 0 && g->chain != 1) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: chain=%d", g->chain);
-    if (g->t_planes != 0 && g->t_planes != 54 && g->t_planes != 81) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: t_planes=%d", g->t_planes);
-    const int t_planes = g->t_planes ? g->t_planes : 54;
-    if (g->chain == 1 && (g->C != 256 || t_planes != 81))
-        return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: the low-pass chain needs C = 256 and an 81-plane t (C=%d, t_planes=%d)", g->C, t_planes);
-    const bool want_ll = g->chain == 0 && g->ll_wp1 && g->ll_wp2;
-    if (want_ll && (g->C != 256 || t_planes != 81))
-        return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: the low-pass chain needs C = 256 and an 81-plane t (C=%d, t_planes=%d)", g->C, t_planes);
-    if (g->mid_out && (g->chain != 0 || g->mid_ct <= 0 || g->mid_off_p < 0 || g->mid_off_n < 0 || g->mid_off_p + g->C > g->mid_ct ||
-                       g->mid_off_n + g->C > g->mid_ct || (want_ll && (g->mid_off_ll < 0 || g->mid_off_ll + g->C / 4 > g->mid_ct))))
-        return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: mid_out needs chain = 0 and channel offsets inside mid_ct = %d", g->mid_ct);
-    if (g->chain == 0) {
-        const int took = head_chain_launch(g, t_planes, (hipStream_t)stream);
-        int st = took ? check_launch("head_chain_kernel") : WMD_OK;
-        if (st) return st;
-        if (g->mid_out && (!took || (want_ll && took != 2)))
-            return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: mid_out is written by the chained kernel only (C = 64, 128, 256, H*W %% 4 == 0)");
-        if (want_ll && took != 2) {   // the chained kernel did not take the low-pass chain along: a launch of its own
-            wmd_head_fused_args l = *g;
-            l.wp1 = g->ll_wp1;
-            l.bias1 = g->ll_bias1;
-            l.wp2 = g->ll_wp2;
-            l.chain = 1;
-            l.run_mask = nullptr;
-            l.ll_wp1 = l.ll_wp2 = l.ll_bias1 = nullptr;
-            st = wmd_head_fused_fwd(&l, stream);
-            if (st) return st;
-        }
-        if (took) return WMD_OK;
-    }
-    const int rows = g->chain == 1 ? g->C / 4 : 2 * g->C;   // stacked mid channels of this launch
+// The FUSE instantiations of conv_fwd_kernel for the wavelet heads (wmd_internal.h; called, after validation, by the fused-head
+// entry points of wmd_head_chain.hip, whose chained kernel takes every launch it can)
+int head_fuse_launch(const float* x, const float* wp1, const float* bias1, const float* wp2, float* t, int B, int plane, int C, float slope, int t_planes, bool low_pass, hipStream_t s) {
+    const int rows = low_pass ? C / 4 : 2 * C;   // stacked mid channels of this launch
     ConvKArgs a;
     memset(&a, 0, sizeof(a));
-    a.x1 = g->x;
-    a.wp = g->wp1;
-    a.bias = g->bias1;
-    a.B = g->B;
+    a.x1 = x;
+    a.wp = wp1;
+    a.bias = bias1;
+    a.B = B;
     a.H = 1;
-    a.W = g->H * g->W;   // 1x1: the image is a flat pixel vector
+    a.W = plane;   // 1x1: the image is a flat pixel vector
     a.H1 = 1;
     a.W1 = a.W;
-    a.C1 = g->C;
-    a.Cin = g->C;
+    a.C1 = C;
+    a.Cin = C;
     a.Cout = rows;
     a.up1 = 1;
     a.act = WMD_ACT_LEAKY;
-    a.slope = g->slope;
-    a.nci4 = frag_dims(rows, g->C).nci4;
-    a.ncot = frag_dims(rows, g->C).ncot;
-    a.nchunks = g->C >= 128 ? g->C / 32 : 1;   // C = 32 / 64: the whole reduction is one LDS-resident chunk
+    a.slope = slope;
+    a.nci4 = frag_dims(rows, C).nci4;
+    a.ncot = frag_dims(rows, C).ncot;
+    a.nchunks = C >= 128 ? C / 32 : 1;   // C = 32 / 64: the whole reduction is one LDS-resident chunk
     a.ksplit = 1;
     a.chunks_per_split = a.nchunks;
     a.tiles_y = 1;
-    a.wp2 = g->wp2;
-    a.t = g->t;
+    a.wp2 = wp2;
+    a.t = t;
     a.t_ctot = t_planes;
-    a.t_row0 = g->chain == 1 ? 54 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    const double pix = (double)g->B * g->H * g->W;
-    if (g->chain == 1) {
+    a.t_row0 = low_pass ? 54 : 0;
+    const double pix = (double)B * plane;
+    if (low_pass) {
         // 64 mid channels = one 16-row tile per wave of a 4-wave block; the second GEMM (K = 64) gives rows 0..8
-        ProfScope prof("conv_fwd_kernel<fused LL head>", 2.0 * pix * (g->C * (g->C / 4.0) + 9.0 * (g->C / 4.0)), 4.0 * pix * (g->C + 9), s);
+        ProfScope prof("conv_fwd_kernel<fused LL head>", 2.0 * pix * (C * (C / 4.0) + 9.0 * (C / 4.0)), 4.0 * pix * (C + 9), s);
         a.tiles_x = (a.W + 31) / 32;
-        hipLaunchKernelGGL((conv_fwd_kernel<1, 32, 1, 2, 4, 1, 32, 1, true>), dim3(g->B * a.tiles_x, 1), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_fwd_kernel<1, 32, 1, 2, 4, 1, 32, 1, true>), dim3(B * a.tiles_x, 1), dim3(256), 0, s, a);
         return check_launch("conv_fwd_kernel<fused LL head>");
     }
-    ProfScope prof("conv_fwd_kernel<fused head>", 2.0 * pix * (2.0 * g->C * g->C + 54.0 * g->C),
-                   4.0 * pix * (g->C + 54), s);
-    if (g->C == 32) {
+    ProfScope prof("conv_fwd_kernel<fused head>", head_gemm_flops(pix, C), 4.0 * pix * (C + 54), s);
+    if (C == 32) {
         a.tiles_x = (a.W + 255) / 256;
-        hipLaunchKernelGGL((conv_fwd_kernel<1, 256, 2, 4, 1, 4, 32, 1, true, 1>), dim3(g->B * a.tiles_x, 2), dim3(256), 0, s, a);
-    } else if (g->C == 64) {
+        hipLaunchKernelGGL((conv_fwd_kernel<1, 256, 2, 4, 1, 4, 32, 1, true, 1>), dim3(B * a.tiles_x, 2), dim3(256), 0, s, a);
+    } else if (C == 64) {
         a.tiles_x = (a.W + 127) / 128;
-        hipLaunchKernelGGL((conv_fwd_kernel<1, 128, 2, 4, 2, 2, 64, 1, true, 1>), dim3(g->B * a.tiles_x, 2), dim3(256), 0, s, a);
-    } else if (g->C == 128) {
+        hipLaunchKernelGGL((conv_fwd_kernel<1, 128, 2, 4, 2, 2, 64, 1, true, 1>), dim3(B * a.tiles_x, 2), dim3(256), 0, s, a);
+    } else if (C == 128) {
         // coarse levels have few pixels: 64- / 32-pixel tiles (53 / 78 KB of LDS: 3 / 2 blocks per CU, 720 / 360 blocks) beat
         // 128- / 64-pixel tiles by 20 % / 8 % although every weight fragment then feeds half as many MFMAs
         a.tiles_x = (a.W + 63) / 64;
-        hipLaunchKernelGGL((conv_fwd_kernel<1, 64, 4, 2, 2, 2, 32, 1, true>), dim3(g->B * a.tiles_x, 2), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_fwd_kernel<1, 64, 4, 2, 2, 2, 32, 1, true>), dim3(B * a.tiles_x, 2), dim3(256), 0, s, a);
     } else {
         a.tiles_x = (a.W + 31) / 32;
-        hipLaunchKernelGGL((conv_fwd_kernel<1, 32, 4, 2, 4, 1, 32, 1, true>), dim3(g->B * a.tiles_x, 2), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_fwd_kernel<1, 32, 4, 2, 4, 1, 32, 1, true>), dim3(B * a.tiles_x, 2), dim3(256), 0, s, a);
     }
     return check_launch("conv_fwd_kernel<fused head>");
 }
+
+}  // namespace wmd
+
+using namespace wmd;
 
 extern "C" int wmd_conv_num_configs(void) { return kNumCfgs; }
 extern "C" const char* wmd_conv_config_name(int i) { return (i >= 0 && i < kNumCfgs) ? kCfgs[i].name : nullptr; }

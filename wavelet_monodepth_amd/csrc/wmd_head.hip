@@ -21,8 +21,6 @@
 
 namespace wmd {
 
-
-
 constexpr int HT_H = 16, HT_W = 32, H_CK = 8, H_TT = 128;  // H_TT threads cover the tile once (4 px each)
 constexpr int H_PH = HT_H + 2;        // 18 patch rows
 constexpr int H_PWV = HT_W + 2;       // 34 valid patch columns
@@ -425,7 +423,6 @@ struct ShiftsumChainArgs {
     int by0, bx0;   // tile of the coarsest level (by0 * bx0 == 16)
 };
 
-
 __global__ __launch_bounds__(256) void head_shiftsum_chain_kernel(const ShiftsumChainArgs c) {
     __shared__ float low[2][256];     // low-pass tiles handed from level k to level k + 1
     // tile of the coarsest level: by0 x bx0 pixels (16 of them), doubling per level up to 256 at the third.  Round 6: 2 x 8 instead
@@ -461,6 +458,49 @@ __global__ __launch_bounds__(256) void head_shiftsum_chain_kernel(const Shiftsum
     }
 }
 
+const HeadSwitches& head_switches() {
+    static const HeadSwitches sw = [] {
+        auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        HeadSwitches s;
+        s.chain = num("WMD_HEAD_CHAIN", 1) != 0;
+        s.chain_multi = s.chain && num("WMD_HEAD_CHAIN_MULTI", 1) != 0;
+        s.chain_pg256 = num("WMD_HEAD_CHAIN_PG256", 0);
+        s.stream = num("WMD_HEAD_STREAM", 1) != 0;
+        s.stream_th = num("WMD_HEAD_STREAM_TH", 0);
+        s.stream_min_pixels = getenv("WMD_HEAD_STREAM_MIN_PIXELS") ? atol(getenv("WMD_HEAD_STREAM_MIN_PIXELS")) : 0L;
+        s.shiftsum_square = num("WMD_SHIFTSUM_CHAIN_SQUARE", 0) != 0;
+        s.csplit = getenv("WMD_HEAD_CSPLIT") ? std::max(1, num("WMD_HEAD_CSPLIT", 1)) : 0;
+        s.ng = getenv("WMD_HEAD_NG") ? (num("WMD_HEAD_NG", 0) == 4 ? 4 : 2) : 0;
+        s.bwd_fused = num("WMD_HEAD_BWD_FUSED", 1) != 0;
+        return s;
+    }();
+    return sw;
+}
+
+int head_check_pad(const char* fn, int pad_mode, int H, int W) {
+    if (pad_mode < 0 || pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "%s: pad_mode=%d", fn, pad_mode);
+    if (pad_mode == WMD_PAD_REFLECT && (H < 2 || W < 2)) return fail(WMD_ERR_BAD_SHAPE, "%s: reflect padding needs H,W >= 2", fn);
+    return WMD_OK;
+}
+
+int head_check_completion_level(const char* fn, bool coarse, int k, const wmd_head_shiftsum_args& c, int B, int H, int W) {
+    const char* lv = coarse ? "coarse level" : "level";
+    if (!c.t || !c.yh || !c.out) return fail(WMD_ERR_BAD_ARG, "%s: %s %d: t, yh and out are required", fn, lv, k);
+    if (c.B != B || c.H != H || c.W != W)
+        return fail(WMD_ERR_BAD_SHAPE, "%s: %s %d is %dx%dx%d, expected %dx%dx%d%s", fn, lv, k, c.B, c.H, c.W, B, H, W, coarse ? "" : " (each level doubles the one before)");
+    // the one rule on which the two entries disagree: a reflect level below 2 x 2 is WMD_ERR_BAD_SHAPE in the chain entry and
+    // WMD_ERR_BAD_ARG (one text with the pad mode range) in the pyramid entry.  Callers may tell them apart, so both answers stay.
+    if (!coarse) {
+        if (int st = head_check_pad(fn, c.pad_mode, c.H, c.W)) return st;
+    } else if (c.pad_mode < 0 || c.pad_mode > 2 || (c.pad_mode == WMD_PAD_REFLECT && (c.H < 2 || c.W < 2)))
+        return fail(WMD_ERR_BAD_ARG, "%s: coarse level %d: pad_mode=%d on %dx%d", fn, k, c.pad_mode, c.H, c.W);
+    if (c.yh_mask || c.range_keys || c.sig_p || c.sig_n || c.sig_ll)
+        return fail(WMD_ERR_UNSUPPORTED, "%s: dense inference only (no yh_mask / range_keys / sigmoid outputs)", fn);
+    if (k == 0 ? ((c.yl != nullptr) == (c.yl_out != nullptr)) : (c.yl != nullptr || c.yl_out != nullptr))
+        return fail(WMD_ERR_BAD_ARG, "%s: the first %s takes exactly one of yl / yl_out, the others %sthe chain's low-pass", fn, lv, coarse ? "" : "take ");
+    return WMD_OK;
+}
+
 static void head_plan(const wmd_head_args* g, int* tiles_x, int* tiles_y, int* csplit, int* cper) {
     *tiles_x = (g->W + HT_W - 1) / HT_W;
     *tiles_y = (g->H + HT_H - 1) / HT_H;
@@ -468,7 +508,7 @@ static void head_plan(const wmd_head_args* g, int* tiles_x, int* tiles_y, int* c
     // few tiles (coarse pyramid levels, up to 256 channels each): slice the channel loop over blocks so that
     // ~3 blocks per CU are in flight; a slice is at least two 8-channel chunks
     int cs = (int)std::min<long>((3L * kNumCU + tiles - 1) / tiles, std::max(1, g->C / 16));
-    if (const char* e = getenv("WMD_HEAD_CSPLIT")) cs = std::max(1, atoi(e));
+    if (head_switches().csplit) cs = head_switches().csplit;
     cs = std::max(1, std::min(cs, (g->C + H_CK - 1) / H_CK));
     int per = (g->C + cs - 1) / cs;
     per = ((per + H_CK - 1) / H_CK) * H_CK;
@@ -495,9 +535,7 @@ extern "C" int wmd_head3x3_fwd(const wmd_head_args* g, void* stream) {
     if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->C <= 0)
         return fail(WMD_ERR_BAD_SHAPE, "wmd_head3x3_fwd: B=%d H=%d W=%d C=%d", g->B, g->H, g->W, g->C);
     if (g->Cout < 1 || g->Cout > 4) return fail(WMD_ERR_UNSUPPORTED, "wmd_head3x3_fwd: Cout=%d (1..4)", g->Cout);
-    if (g->pad_mode < 0 || g->pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "wmd_head3x3_fwd: pad_mode=%d", g->pad_mode);
-    if (g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_head3x3_fwd: reflect padding needs H,W >= 2");
+    if (int st = head_check_pad("wmd_head3x3_fwd", g->pad_mode, g->H, g->W)) return st;
     int tiles_x, tiles_y, csplit, cper;
     head_plan(g, &tiles_x, &tiles_y, &csplit, &cper);
     if (csplit > 1 && (!g->workspace || g->workspace_floats < (size_t)csplit * g->B * 2 * g->Cout * g->H * g->W)) {
@@ -510,7 +548,7 @@ extern "C" int wmd_head3x3_fwd(const wmd_head_args* g, void* stream) {
     ProfScope prof("head3x3_kernel", sides * 18.0 * g->C * g->Cout * pix, 4.0 * pix * (sides * g->C + g->Cout), s);
     // few tiles (coarse pyramid levels): 4 channel groups per tile; otherwise 2
     bool wide = (size_t)g->B * tiles_x * tiles_y * csplit < 2 * (size_t)kNumCU;
-    if (const char* e = getenv("WMD_HEAD_NG")) wide = atoi(e) == 4;
+    if (head_switches().ng) wide = head_switches().ng == 4;
 #define WMD_HEAD_LAUNCH(CO)                                                                                   \
     if (wide) hipLaunchKernelGGL((head3x3_kernel<CO, 4>), grid, dim3(H_TT * 4), 0, s, *g, tiles_x, tiles_y, csplit, cper, g->workspace); \
     else hipLaunchKernelGGL((head3x3_kernel<CO, 2>), grid, dim3(H_TT * 2), 0, s, *g, tiles_x, tiles_y, csplit, cper, g->workspace)
@@ -534,24 +572,11 @@ extern "C" int wmd_head_shiftsum_chain_fwd(const wmd_head_shiftsum_args* levels,
     ShiftsumChainArgs c;
     c.n = n_levels;
     for (int k = 0; k < n_levels; ++k) {
-        const wmd_head_shiftsum_args& g = levels[k];
-        if (!g.t || !g.yh || !g.out) return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_chain_fwd: level %d: t, yh and out are required", k);
-        if (g.B != levels[0].B || g.H != (levels[0].H << k) || g.W != (levels[0].W << k))
-            return fail(WMD_ERR_BAD_SHAPE, "wmd_head_shiftsum_chain_fwd: level %d is %dx%dx%d, expected %dx%dx%d (each level doubles the one before)",
-                        k, g.B, g.H, g.W, levels[0].B, levels[0].H << k, levels[0].W << k);
-        if (g.pad_mode < 0 || g.pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_chain_fwd: pad_mode=%d", g.pad_mode);
-        if (g.pad_mode == WMD_PAD_REFLECT && (g.H < 2 || g.W < 2)) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_shiftsum_chain_fwd: reflect padding needs H,W >= 2");
-        if (g.yh_mask || g.range_keys || g.sig_p || g.sig_n || g.sig_ll)
-            return fail(WMD_ERR_UNSUPPORTED, "wmd_head_shiftsum_chain_fwd: dense inference only (no yh_mask / range_keys / sigmoid outputs)");
-        if (k == 0 ? ((g.yl != nullptr) == (g.yl_out != nullptr)) : (g.yl != nullptr || g.yl_out != nullptr))
-            return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_chain_fwd: the first level takes exactly one of yl / yl_out, the others take the chain's low-pass");
-        c.lv[k] = g;
+        if (int st = head_check_completion_level("wmd_head_shiftsum_chain_fwd", false, k, levels[k], levels[0].B, levels[0].H << k, levels[0].W << k)) return st;
+        c.lv[k] = levels[k];
     }
     for (int k = n_levels; k < 3; ++k) c.lv[k] = levels[0];
-    static const int square = [] {
-        const char* e = getenv("WMD_SHIFTSUM_CHAIN_SQUARE");
-        return e ? atoi(e) : 0;
-    }();
+    const bool square = head_switches().shiftsum_square;
     c.by0 = square ? 4 : 2;
     c.bx0 = square ? 4 : 8;
     const int tiles = ((levels[0].W + c.bx0 - 1) / c.bx0) * ((levels[0].H + c.by0 - 1) / c.by0);
@@ -567,9 +592,7 @@ extern "C" int wmd_head_shiftsum_fwd(const wmd_head_shiftsum_args* g, void* stre
     if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_fwd: null args");
     if (!g->t || !g->yh) return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_fwd: null tensor pointer");
     if (g->B <= 0 || g->H <= 0 || g->W <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_shiftsum_fwd: B=%d H=%d W=%d", g->B, g->H, g->W);
-    if (g->pad_mode < 0 || g->pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_fwd: pad_mode=%d", g->pad_mode);
-    if (g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_head_shiftsum_fwd: reflect padding needs H,W >= 2");
+    if (int st = head_check_pad("wmd_head_shiftsum_fwd", g->pad_mode, g->H, g->W)) return st;
     if (g->yl_out && g->yl) return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_fwd: yl_out (low-pass head completed here) excludes yl");
     if ((g->out != nullptr) != (g->yl != nullptr || g->yl_out != nullptr))
         return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_fwd: yl (or yl_out) and out go together");
@@ -577,7 +600,7 @@ extern "C" int wmd_head_shiftsum_fwd(const wmd_head_shiftsum_args* g, void* stre
         return fail(WMD_ERR_BAD_ARG, "wmd_head_shiftsum_fwd: sig_p and sig_n go together, sig_ll needs yl_out, neither takes a yh_mask");
     const size_t n = (size_t)g->B * g->H * g->W;
     hipStream_t s = (hipStream_t)stream;
-    ProfScope prof("head_shiftsum_kernel", 60.0 * n, 4.0 * n * ((g->yl_out ? 64 : 54) + 3 + (g->out ? (g->disp ? 9 : 5) : 0)), s);
+    ProfScope prof("head_shiftsum_kernel", 60.0 * n, head_level_bytes(n, g->yl_out ? 64 : 54, g->out, g->disp), s);
     const unsigned threads = n < 65536 ? 64 : 256;   // coarse levels: one wavefront per block spreads the few pixels over the CUs
     hipLaunchKernelGGL(head_shiftsum_kernel, dim3((unsigned)std::min<size_t>((n + threads - 1) / threads, (size_t)kNumCU * 16)), dim3(threads),
                        0, s, *g);

@@ -1004,8 +1004,7 @@ extern "C" int wmd_head3x3_bwd(const wmd_head3x3_bwd_args* g, void* stream) {
 // may both stages run as head_bwd_fused32_kernel?  (two 3-channel heads of 32 channels each over a 32-channel x, whole 64-pixel
 // tiles, rows that are multiples of four pixels; WMD_HEAD_BWD_FUSED=0: never)
 static bool head_bwd_fused_ok(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_bwd_args* a1) {
-    static const bool on = !(getenv("WMD_HEAD_BWD_FUSED") && atoi(getenv("WMD_HEAD_BWD_FUSED")) == 0);
-    if (!on || a3->n_heads != 2 || a3->Ct != 64 || a1->C != 32 || !a1->dx || a3->pad_mode != WMD_PAD_REFLECT) return false;   // (the decoders' padding: what the tests cover)
+    if (!head_switches().bwd_fused || a3->n_heads != 2 || a3->Ct != 64 || a1->C != 32 || !a1->dx || a3->pad_mode != WMD_PAD_REFLECT) return false;   // (the decoders' padding: what the tests cover)
     for (int k = 0; k < 2; ++k)
         if (a3->head[k].nrows != 3 || a3->head[k].nch != 32 || (a3->head[k].ch0 != 0 && a3->head[k].ch0 != 32)) return false;
     if (a3->head[0].ch0 == a3->head[1].ch0) return false;

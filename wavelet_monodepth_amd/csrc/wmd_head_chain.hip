@@ -23,7 +23,6 @@
 // groups of a block share the weight chunk.  x rows are padded to a stride == 16 (mod 32) floats: the four K-lanes of a
 // fragment read hit disjoint banks.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 #include "wmd_internal.h"
@@ -371,12 +370,11 @@ struct HeadChainMulti {
     int first[4];   // block ranges: level k owns [first[k], first[k + 1]) = (its B * tiles blocks of side 0, then of side 1)
     int n;
 };
-constexpr int head_chain_multi_lds() {
-    int m = HeadChainTile<256, 4, 1, 1, 4>::LDS_FLOATS;
-    if (HeadChainTile<128, 1, 4, 1, 8>::LDS_FLOATS > m) m = HeadChainTile<128, 1, 4, 1, 8>::LDS_FLOATS;
-    if (HeadChainTile<64, 1, 4, 2, 16>::LDS_FLOATS > m) m = HeadChainTile<64, 1, 4, 2, 16>::LDS_FLOATS;
-    return m;
-}
+// the merged launch's tile per width (head_chain_multi_kernel runs head_chain_body with the same arguments)
+using ChainMulti256 = HeadChainTile<256, 4, 1, 1, 4>;
+using ChainMulti128 = HeadChainTile<128, 1, 4, 1, 8>;
+using ChainMulti64 = HeadChainTile<64, 1, 4, 2, 16>;
+constexpr int head_chain_multi_lds() { return std::max({ChainMulti256::LDS_FLOATS, ChainMulti128::LDS_FLOATS, ChainMulti64::LDS_FLOATS}); }
 __global__ __launch_bounds__(256, 3) void head_chain_multi_kernel(const HeadChainMulti m) {
     __shared__ __attribute__((aligned(16))) float lds[head_chain_multi_lds()];
     int k = 0;
@@ -408,8 +406,6 @@ static void launch_chain(const HeadChainArgs& a, int B, hipStream_t s) {
     hipLaunchKernelGGL((head_chain_kernel<C, RS, PG, NT, KC, PD>), dim3((unsigned)(B * k.tiles), 2), dim3(T::NTH), 0, s, k);
 }
 
-// -> true when the chained form took the launch (C = 64 / 128 / 256, image planes of a multiple of 4 pixels; WMD_HEAD_CHAIN=0
-// keeps the FUSE form of conv_fwd_kernel)
 static HeadChainArgs head_chain_args(const wmd_head_fused_args* g, int t_planes, long plane, bool& with_ll) {
     HeadChainArgs a;
     a.x = g->x;
@@ -435,17 +431,18 @@ static HeadChainArgs head_chain_args(const wmd_head_fused_args* g, int t_planes,
     return a;
 }
 
-int head_chain_launch(const wmd_head_fused_args* g, int t_planes, hipStream_t s) {
-    static const bool on = [] {
-        const char* e = getenv("WMD_HEAD_CHAIN");
-        return !(e && atoi(e) == 0);
-    }();
+// can the chained kernel take this level?  (C = 64 / 128 / 256; planes of a multiple of 4 pixels: chain_fetch's 16-byte pieces)
+static bool head_chain_admits(long plane, int C) { return !(plane & 3) && plane <= (1L << 28) && (C == 64 || C == 128 || C == 256); }
+
+// the chained form of wmd_head_fused_fwd (chain = 0) -> 0 not taken (a level the kernel does not admit; WMD_HEAD_CHAIN=0 keeps the FUSE
+// form of conv_fwd_kernel), 1 taken, 2 taken together with the low-pass chain (wmd_head_fused_args.ll_wp1)
+static int head_chain_launch(const wmd_head_fused_args* g, int t_planes, hipStream_t s) {
     const long plane = (long)g->H * g->W;
-    if (!on || (plane & 3) || plane > (1L << 28) || (g->C != 64 && g->C != 128 && g->C != 256)) return 0;
+    if (!head_switches().chain || !head_chain_admits(plane, g->C)) return 0;
     bool with_ll = false;
     HeadChainArgs a = head_chain_args(g, t_planes, plane, with_ll);
     const double pix = (double)g->B * plane;
-    ProfScope prof("head_chain_kernel", 2.0 * pix * (2.0 * g->C * g->C + 54.0 * g->C), 4.0 * pix * (g->C + 54), s);
+    ProfScope prof("head_chain_kernel", head_gemm_flops(pix, g->C), 4.0 * pix * (g->C + 54), s);
     // (pixel-tile / wave-count / chunk variants -- 64 to 256 pixels, 2 to 16 waves, channel split 1 / 2 / 4 / 8 -- all measured
     //  within +-2 us of these)
     if (g->C == 64)
@@ -456,10 +453,7 @@ int head_chain_launch(const wmd_head_fused_args* g, int t_planes, hipStream_t s)
         // 32 pixels (8 waves: 4 share a pixel group's 256 channels), 16 chunks -- or 48 pixels (12 waves) when that brings the launch down
         // to one block per CU: the level has so few pixels that whole blocks per CU is what its time is made of (config 2, batch 12:
         // 360 blocks = two on 104 CUs, one on 152 -> 240 blocks, one each; profiles/r06_notes.md section 6)
-        static const int pg_force = [] {
-            const char* e = getenv("WMD_HEAD_CHAIN_PG256");
-            return e ? atoi(e) : 0;
-        }();
+        const int pg_force = head_switches().chain_pg256;
         const long b32 = (long)g->B * ((plane + 31) / 32) * 2, b48 = (long)g->B * ((plane + 47) / 48) * 2;
         const long cost32 = ((b32 + kNumCU - 1) / kNumCU) * 2, cost48 = ((b48 + kNumCU - 1) / kNumCU) * 3;
         if (pg_force == 3 || (pg_force == 0 && cost48 < cost32)) launch_chain<256, 4, 3, 1, 4, WMD_CHAIN_PD256>(a, g->B, s);
@@ -468,15 +462,10 @@ int head_chain_launch(const wmd_head_fused_args* g, int t_planes, hipStream_t s)
     return with_ll ? 2 : 1;
 }
 
-// -> levels taken (n) or 0: the merged launch needs every level to be a chained width with planes of a multiple of 4 pixels, no
-// run mask and no training outputs (WMD_HEAD_CHAIN_MULTI=0 off)
-int head_chain_multi_launch(const wmd_head_fused_args* g, int n, hipStream_t s) {
-    static const bool on = [] {
-        const char* e = getenv("WMD_HEAD_CHAIN_MULTI");
-        const char* c = getenv("WMD_HEAD_CHAIN");
-        return !(e && atoi(e) == 0) && !(c && atoi(c) == 0);
-    }();
-    if (!on || n < 1 || n > 3) return 0;
+// -> levels taken (n) or 0: the merged launch needs every level to be one the chained kernel admits, with no run mask and no
+// training outputs (WMD_HEAD_CHAIN_MULTI=0 off)
+static int head_chain_multi_launch(const wmd_head_fused_args* g, int n, hipStream_t s) {
+    if (!head_switches().chain_multi || n < 1 || n > 3) return 0;
     HeadChainMulti m;
     m.n = n;
     m.first[0] = 0;
@@ -484,18 +473,17 @@ int head_chain_multi_launch(const wmd_head_fused_args* g, int n, hipStream_t s) 
     for (int k = 0; k < n; ++k) {
         const long plane = (long)g[k].H * g[k].W;
         const int t_planes = g[k].t_planes ? g[k].t_planes : 54;
-        if ((plane & 3) || plane > (1L << 28) || (g[k].C != 64 && g[k].C != 128 && g[k].C != 256) || g[k].run_mask || g[k].mid_out || g[k].chain != 0)
-            return 0;
+        if (!head_chain_admits(plane, g[k].C) || g[k].run_mask || g[k].mid_out || g[k].chain != 0) return 0;
         if (g[k].ll_wp1 && (g[k].C != 256 || t_planes != 81 || !g[k].ll_wp2)) return 0;
         bool with_ll = false;
         m.lv[k] = head_chain_args(&g[k], t_planes, plane, with_ll);
-        const int pxb = g[k].C == 256 ? 16 : (g[k].C == 128 ? 64 : 128);
+        const int pxb = g[k].C == 256 ? ChainMulti256::PXB : (g[k].C == 128 ? ChainMulti128::PXB : ChainMulti64::PXB);
         m.lv[k].tiles = (int)((plane + pxb - 1) / pxb);
         const long blocks = 2L * g[k].B * m.lv[k].tiles;
         if (m.first[k] + blocks > (1L << 30)) return 0;
         m.first[k + 1] = m.first[k] + (int)blocks;
         const double pix = (double)g[k].B * plane;
-        flops += 2.0 * pix * (2.0 * g[k].C * g[k].C + 54.0 * g[k].C);
+        flops += head_gemm_flops(pix, g[k].C);
         bytes += 4.0 * pix * (g[k].C + 54);
     }
     ProfScope prof("head_chain_multi_kernel", flops, bytes, s);
@@ -504,3 +492,49 @@ int head_chain_multi_launch(const wmd_head_fused_args* g, int n, hipStream_t s) 
 }
 
 }  // namespace wmd
+
+using namespace wmd;
+
+extern "C" int wmd_head_fused_multi_fwd(const wmd_head_fused_args* levels, int n_levels, void* stream) {
+    if (!levels || n_levels < 1 || n_levels > 3) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_multi_fwd: 1..3 levels (got %d)", n_levels);
+    for (int k = 0; k < n_levels; ++k) {
+        const wmd_head_fused_args* g = &levels[k];
+        if (!g->x || !g->wp1 || !g->wp2 || !g->t) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_multi_fwd: level %d: null tensor pointer", k);
+        if (g->B <= 0 || g->H <= 0 || g->W <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_fused_multi_fwd: level %d: B=%d H=%d W=%d", k, g->B, g->H, g->W);
+    }
+    if (head_chain_multi_launch(levels, n_levels, (hipStream_t)stream)) return check_launch("head_chain_multi_kernel");
+    for (int k = 0; k < n_levels; ++k) {      // a level the merged launch cannot take: the per-level launches, same planes
+        if (int st = wmd_head_fused_fwd(&levels[k], stream)) return st;
+    }
+    return WMD_OK;
+}
+
+extern "C" int wmd_head_fused_fwd(const wmd_head_fused_args* g, void* stream) {
+    if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: null args");
+    if (!g->x || !g->wp1 || !g->wp2 || !g->t) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: null tensor pointer");
+    if (g->B <= 0 || g->H <= 0 || g->W <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_fused_fwd: B=%d H=%d W=%d", g->B, g->H, g->W);
+    if (g->C != 32 && g->C != 64 && g->C != 128 && g->C != 256)
+        return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: C=%d (32, 64, 128 or 256; other widths run unfused)", g->C);
+    if (g->chain != 0 && g->chain != 1) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: chain=%d", g->chain);
+    if (g->t_planes != 0 && g->t_planes != 54 && g->t_planes != 81) return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: t_planes=%d", g->t_planes);
+    const int t_planes = g->t_planes ? g->t_planes : 54;
+    const bool want_ll = g->chain == 0 && g->ll_wp1 && g->ll_wp2;
+    if ((g->chain == 1 || want_ll) && (g->C != 256 || t_planes != 81))
+        return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: the low-pass chain needs C = 256 and an 81-plane t (C=%d, t_planes=%d)", g->C, t_planes);
+    if (g->mid_out && (g->chain != 0 || g->mid_ct <= 0 || g->mid_off_p < 0 || g->mid_off_n < 0 || g->mid_off_p + g->C > g->mid_ct ||
+                       g->mid_off_n + g->C > g->mid_ct || (want_ll && (g->mid_off_ll < 0 || g->mid_off_ll + g->C / 4 > g->mid_ct))))
+        return fail(WMD_ERR_BAD_ARG, "wmd_head_fused_fwd: mid_out needs chain = 0 and channel offsets inside mid_ct = %d", g->mid_ct);
+    hipStream_t s = (hipStream_t)stream;
+    auto fuse = [&](const float* wp1, const float* bias1, const float* wp2, bool low_pass) {   // the FUSE form of conv_fwd_kernel
+        return head_fuse_launch(g->x, wp1, bias1, wp2, g->t, g->B, g->H * g->W, g->C, g->slope, t_planes, low_pass, s);
+    };
+    if (g->chain == 1) return fuse(g->wp1, g->bias1, g->wp2, true);
+    const int took = head_chain_launch(g, t_planes, s);
+    if (took)
+        if (int st = check_launch("head_chain_kernel")) return st;
+    if (g->mid_out && (!took || (want_ll && took != 2)))
+        return fail(WMD_ERR_UNSUPPORTED, "wmd_head_fused_fwd: mid_out is written by the chained kernel only (C = 64, 128, 256, H*W %% 4 == 0)");
+    if (want_ll && took != 2)   // the chained kernel did not take the low-pass chain along: a launch of its own
+        if (int st = fuse(g->ll_wp1, g->ll_bias1, g->ll_wp2, true)) return st;
+    return took ? WMD_OK : fuse(g->wp1, g->bias1, g->wp2, false);
+}

@@ -349,9 +349,7 @@ extern "C" int wmd_head_level_fwd(const wmd_head_level_args* g, void* stream) {
     if (g->B <= 0 || g->H <= 0 || g->W <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_head_level_fwd: B=%d H=%d W=%d", g->B, g->H, g->W);
     if (!wmd_head_level_supported(g->C))
         return fail(WMD_ERR_UNSUPPORTED, "wmd_head_level_fwd: C=%d (32 only; use wmd_head_fused_fwd + wmd_head_shiftsum_fwd)", g->C);
-    if (g->pad_mode < 0 || g->pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "wmd_head_level_fwd: pad_mode=%d", g->pad_mode);
-    if (g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_head_level_fwd: reflect padding needs H,W >= 2");
+    if (int st = head_check_pad("wmd_head_level_fwd", g->pad_mode, g->H, g->W)) return st;
     if ((g->out != nullptr) != (g->yl != nullptr)) return fail(WMD_ERR_BAD_ARG, "wmd_head_level_fwd: yl and out go together");
     if (g->disp && !g->out) return fail(WMD_ERR_BAD_ARG, "wmd_head_level_fwd: disp needs out");
     if ((double)g->C * g->H * g->W * 4 > 2147483647.0)
@@ -364,8 +362,7 @@ extern "C" int wmd_head_level_fwd(const wmd_head_level_args* g, void* stream) {
     if (head_stream_launch(g, nullptr, 0, s)) return check_launch("head_stream_kernel");   // round 6: plain inference outputs stream (wmd_head_stream.hip)
     const int tiles_x = (g->W + HL_TW - 1) / HL_TW, tiles_y = (g->H + HL_TH - 1) / HL_TH;
     const double pix = (double)g->B * g->H * g->W;
-    ProfScope prof("head_level_kernel", 2.0 * pix * (2.0 * g->C * g->C + 54.0 * g->C),
-                   4.0 * pix * (g->C + 3 + (g->out ? (g->disp ? 9 : 5) : 0)), s);
+    ProfScope prof("head_level_kernel", head_gemm_flops(pix, g->C), head_level_bytes(pix, g->C, g->out, g->disp), s);
     const int ntiles = g->B * tiles_x * tiles_y;
     const dim3 grid((unsigned)std::min(ntiles, 2 * kNumCU));   // persistent: 70 KB of LDS = 2 blocks per CU
     hipLaunchKernelGGL((head_level_kernel<32, 4>), grid, dim3(256), 0, s, *g, tiles_x, tiles_y, ntiles);
@@ -390,19 +387,8 @@ extern "C" int wmd_head_level_pyramid_fwd(const wmd_head_level_args* g, const wm
     if (!wmd_head_level_pyramid_supported(g->C, g->B, g->H, g->W))
         return fail(WMD_ERR_UNSUPPORTED, "wmd_head_level_pyramid_fwd: C=%d %dx%d (C = 32, sizes that are multiples of 8)", g->C, g->H, g->W);
     if ((double)g->C * g->H * g->W * 4 > 2147483647.0) return fail(WMD_ERR_UNSUPPORTED, "wmd_head_level_pyramid_fwd: a per-image tensor slice exceeds 2 GiB");
-    for (int k = 0; k < n_coarse; ++k) {
-        const wmd_head_shiftsum_args& c = coarse[k];
-        const int sh = n_coarse - k;
-        if (!c.t || !c.yh || !c.out) return fail(WMD_ERR_BAD_ARG, "wmd_head_level_pyramid_fwd: coarse level %d: t, yh and out are required", k);
-        if (c.B != g->B || c.H != (g->H >> sh) || c.W != (g->W >> sh) || (c.H << sh) != g->H || (c.W << sh) != g->W)
-            return fail(WMD_ERR_BAD_SHAPE, "wmd_head_level_pyramid_fwd: coarse level %d is %dx%dx%d, expected %dx%dx%d", k, c.B, c.H, c.W, g->B, g->H >> sh, g->W >> sh);
-        if (c.pad_mode < 0 || c.pad_mode > 2 || (c.pad_mode == WMD_PAD_REFLECT && (c.H < 2 || c.W < 2)))
-            return fail(WMD_ERR_BAD_ARG, "wmd_head_level_pyramid_fwd: coarse level %d: pad_mode=%d on %dx%d", k, c.pad_mode, c.H, c.W);
-        if (c.yh_mask || c.range_keys || c.sig_p || c.sig_n || c.sig_ll)
-            return fail(WMD_ERR_UNSUPPORTED, "wmd_head_level_pyramid_fwd: dense inference only (no yh_mask / range_keys / sigmoid outputs)");
-        if (k == 0 ? ((c.yl != nullptr) == (c.yl_out != nullptr)) : (c.yl != nullptr || c.yl_out != nullptr))
-            return fail(WMD_ERR_BAD_ARG, "wmd_head_level_pyramid_fwd: the first coarse level takes exactly one of yl / yl_out, the others the chain's low-pass");
-    }
+    for (int k = 0; k < n_coarse; ++k)   // (H and W are multiples of 8 and n_coarse <= 3: the shifts are exact)
+        if (int st = head_check_completion_level("wmd_head_level_pyramid_fwd", true, k, coarse[k], g->B, g->H >> (n_coarse - k), g->W >> (n_coarse - k))) return st;
     if (!head_stream_launch(g, coarse, n_coarse, (hipStream_t)stream))
         return fail(WMD_ERR_UNSUPPORTED, "wmd_head_level_pyramid_fwd: the streaming kernel is switched off (WMD_HEAD_STREAM=0)");
     return check_launch("head_stream_kernel");

@@ -481,10 +481,7 @@ __global__ __launch_bounds__((HS_NG + HS_NE) * 64, 3) void head_stream_kernel(co
 // 62.0 us, 240 units of 48 rows 57.5 us: the matrix pipe and the vector ALU are one resource, a second block's waves mostly
 // queue behind the first's) -- so prefer one block per CU as long as that fills the chip; ties -> the taller segment (less halo)
 static int head_stream_pick_th(int B, int H, int strips, bool pyramid, double* cost_out = nullptr) {
-    static const int forced = [] {
-        const char* e = getenv("WMD_HEAD_STREAM_TH");
-        return e ? atoi(e) : 0;
-    }();
+    const int forced = head_switches().stream_th;
     if (forced > 0) return pyramid ? std::min(((std::min(forced, H) + 7) / 8) * 8, HS_PYR_TH_MAX) : std::min(forced, H);
     double best = 1e300;
     int best_th = std::min(H, 24);
@@ -516,19 +513,11 @@ int head_stream_pyramid_pays(int B, int H, int W) {
 
 // -> 1 when the streaming kernel took the launch (C = 32, no sparse / training outputs, 0 <= slope <= 1; WMD_HEAD_STREAM=0 off)
 int head_stream_launch(const wmd_head_level_args* g, const wmd_head_shiftsum_args* coarse, int n_coarse, hipStream_t s) {
-    static const bool on = [] {
-        const char* e = getenv("WMD_HEAD_STREAM");
-        return !(e && atoi(e) == 0);
-    }();
-    if (!on || g->C != HS_C || g->yh_mask || g->mid_out || g->sig_p || g->sig_n || g->pad_mode != WMD_PAD_REFLECT) return 0;
+    if (!head_switches().stream || g->C != HS_C || g->yh_mask || g->mid_out || g->sig_p || g->sig_n || g->pad_mode != WMD_PAD_REFLECT) return 0;
     if (!(g->slope >= 0.f && g->slope <= 1.f)) return 0;
     // small maps stay on the one-shot tile kernel: a streaming block needs ~5 steps to fill and drain its pipeline (2 x 12 x 40:
     // 17.1 vs 13.5 us, one 96 x 320 frame: 17.2 vs 15.2 us)
-    static const long min_pixels = [] {
-        const char* e = getenv("WMD_HEAD_STREAM_MIN_PIXELS");
-        return e ? atol(e) : 0L;
-    }();
-    if ((long)g->B * g->H * g->W < min_pixels) return 0;
+    if ((long)g->B * g->H * g->W < head_switches().stream_min_pixels) return 0;
     HeadStreamGeom gm;
     gm.strips = (g->W + HS_TW - 1) / HS_TW;
     HeadStreamPyr pyr;
@@ -549,8 +538,7 @@ int head_stream_launch(const wmd_head_level_args* g, const wmd_head_shiftsum_arg
     gm.dbg = getenv("WMD_HS_DBG") ? atoi(getenv("WMD_HS_DBG")) : 0;
 #endif
     const double pix = (double)g->B * g->H * g->W;
-    ProfScope prof("head_stream_kernel", 2.0 * pix * (2.0 * g->C * g->C + 54.0 * g->C),
-                   4.0 * pix * (g->C + 3 + (g->out ? (g->disp ? 9 : 5) : 0)), s);
+    ProfScope prof("head_stream_kernel", head_gemm_flops(pix, g->C), head_level_bytes(pix, g->C, g->out, g->disp), s);
     // what the matrix pipe executes: every patch position of every unit through 2 x (C x C + 32 x C) MACs
     {
         double pos = 0;

@@ -78,11 +78,30 @@ __device__ __forceinline__ bool pad_coord(int& g, int n, int pad_mode) {
     return true;
 }
 
-// wmd_head_chain.hip: the chained-GEMM form of wmd_head_fused_fwd (chain = 0); false = not taken (unsupported shape / switched off)
-// -> 0 not taken, 1 taken, 2 taken together with the low-pass chain (wmd_head_fused_args.ll_wp1)
-int head_chain_launch(const wmd_head_fused_args* g, int t_planes, hipStream_t s);
-// round 6: the chained first stages of up to three levels in ONE launch (0 = not taken; wmd_head_fused_multi_fwd)
-int head_chain_multi_launch(const wmd_head_fused_args* levels, int n, hipStream_t s);
+// The wavelet heads' front end.  Every WMD_HEAD* / WMD_SHIFTSUM* switch, read once per process (wmd_head.hip):
+struct HeadSwitches {
+    bool chain;              // WMD_HEAD_CHAIN=0: the two-launch heads stay on the FUSE form of conv_fwd_kernel
+    bool chain_multi;        // WMD_HEAD_CHAIN_MULTI=0 (or chain off): every level's first stage as a launch of its own
+    int chain_pg256;         // WMD_HEAD_CHAIN_PG256=2 / 3 forces the C = 256 chain block to 32 / 48 pixels (0: by block count)
+    bool stream;             // WMD_HEAD_STREAM=0: the C = 32 level stays on head_level_kernel
+    int stream_th;           // WMD_HEAD_STREAM_TH=<rows> forces the streaming kernel's segment height (0: the host's model)
+    long stream_min_pixels;  // WMD_HEAD_STREAM_MIN_PIXELS: B*H*W from which the streaming kernel runs (0)
+    bool shiftsum_square;    // WMD_SHIFTSUM_CHAIN_SQUARE=1: 4 x 4 completion tiles instead of 2 x 8
+    int csplit;              // WMD_HEAD_CSPLIT=<n> forces head3x3_kernel's channel split (0: the planner's)
+    int ng;                  // WMD_HEAD_NG=<n> forces head3x3_kernel's channel groups: 4, anything else 2 (0: by tile count)
+    bool bwd_fused;          // WMD_HEAD_BWD_FUSED=0: the C = 32 backward never runs as head_bwd_fused32_kernel
+};
+const HeadSwitches& head_switches();
+// what ProfScope records for the two GEMMs of a level's +- heads, and for the bytes of a level that ends in yh (+ out (+ disp))
+inline double head_gemm_flops(double pix, int C) { return 2.0 * pix * (2.0 * C * C + 54.0 * C); }
+inline double head_level_bytes(double pix, int in_planes, bool out, bool disp) { return 4.0 * pix * (in_planes + 3 + (out ? (disp ? 9 : 5) : 0)); }
+// wmd_head.hip, under the entry point's name `fn`: the pad mode's range and H, W >= 2 for reflect; the per-level rules of a completion
+// chain (level k, coarse to fine, must be B x H x W), for wmd_head_shiftsum_chain_fwd and -- `coarse` -- wmd_head_level_pyramid_fwd
+int head_check_pad(const char* fn, int pad_mode, int H, int W);
+int head_check_completion_level(const char* fn, bool coarse, int k, const wmd_head_shiftsum_args& c, int B, int H, int W);
+// wmd_conv_fwd.hip: the FUSE instantiations of conv_fwd_kernel, for what the chained kernel of wmd_head_chain.hip does not take -- a level's +- heads
+// (wp1 / bias1 / wp2 = both sides stacked) or, low_pass, the low-pass chain alone (C = 256 -> planes 54..62 of an 81-plane t)
+int head_fuse_launch(const float* x, const float* wp1, const float* bias1, const float* wp2, float* t, int B, int plane, int C, float slope, int t_planes, bool low_pass, hipStream_t s);
 
 // wmd_head_stream.hip: the streaming form of wmd_head_level_fwd (C = 32, plain inference outputs); 0 = not taken
 int head_stream_launch(const wmd_head_level_args* g, const wmd_head_shiftsum_args* coarse, int n_coarse, hipStream_t s);

@@ -56,8 +56,9 @@ _SHIFTSUM_CHAIN_MAX_PIXELS = int(os.environ.get("WMD_SHIFTSUM_CHAIN_MAX_PIXELS",
 _HEAD_CHAIN_ON = os.environ.get("WMD_HEAD_CHAIN", "1") != "0"            # 0: no chained two-launch head kernels (C = 64 / 128 / 256)
 _HEAD_CHAIN_MULTI = os.environ.get("WMD_HEAD_CHAIN_MULTI", "1") != "0"   # 0: every level's first stage as a launch of its own
 _HEAD_PYRAMID = os.environ.get("WMD_HEAD_PYRAMID", "1") != "0"   # 0: the coarser levels' completions as a launch of their own
+_HEAD_PYRAMID_MIN = 1 if os.environ.get("WMD_HEAD_PYRAMID") == "2" else 2   # 2: wherever the pyramid launch runs (default: where it pays)
+_HEAD_STREAM_ON = os.environ.get("WMD_HEAD_STREAM", "1") != "0"   # 0: no streaming kernel, hence no pyramid launch either
 _TRAIN_FUSED = os.environ.get("WMD_TRAIN_FUSED_HEADS", "1") != "0"   # 0: training forward of the heads on _StackedHeadsFn + idwt_haar
-# (head_level_pyramid_supported also reads WMD_HEAD_STREAM and WMD_HEAD_PYRAMID=2 on every call)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1089,8 +1090,7 @@ def head_shiftsum_chain_nograd(items, scales, disp_scales, scale_ll=1.0, yl=None
 
 def head_level_pyramid_supported(C_, B, H, W):
     """Dense inference: can the C = 32 level run its heads + synthesis AND the coarser levels' completions in one launch?"""
-    return _HEAD_PYRAMID and os.environ.get("WMD_HEAD_STREAM", "1") != "0" and \
-        _lib.lib().wmd_head_level_pyramid_supported(int(C_), int(B), int(H), int(W)) >= (1 if os.environ.get("WMD_HEAD_PYRAMID") == "2" else 2)
+    return _HEAD_PYRAMID and _HEAD_STREAM_ON and _lib.lib().wmd_head_level_pyramid_supported(int(C_), int(B), int(H), int(W)) >= _HEAD_PYRAMID_MIN
 
 
 def head_level_pyramid_nograd(x, head_p, head_n, scale, disp_scale, items, scales, disp_scales, scale_ll=1.0, yl=None, clamp01=True):
