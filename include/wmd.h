@@ -774,6 +774,37 @@ int wmd_smooth_fwd(const float* disp, const float* img, float* out, int B, int C
 int wmd_smooth_bwd(const float* disp, const float* img, const float* grad_out, float* ddisp, int B, int C, int H, int W,
                    float gamma, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * Pose networks: from the pose trunk's last feature map to cam_T_cam, forward and backward
+ * ------------------------------------------------------------------ */
+
+/* transformation_from_parameters (KITTI/layers.py:42-117).  axisangle, translation [N,3], T [N,4,4] row-major.
+ *   angle = |v|, a = v / (angle + 1e-7) (not renormalised), R = cos(angle) I + (1 - cos(angle)) a a^T + sin(angle) [a]x
+ *   invert == 0: T = [[R, t], [0, 1]]        invert != 0: T = [[R^T, -R^T t], [0, 1]]
+ * 1 - cos is evaluated as 2 sin^2(angle / 2).  At v = 0 the rotation block is the identity exactly.
+ * Backward: dT [N,4,4] -> d_axisangle, d_translation [N,3], the derivative of the expression above (the 1e-7 included;
+ * d|v|/dv = 0 at v = 0, where d_axisangle is exactly 0).  N == 0 is a no-op; one launch each.                          */
+int wmd_pose_transform_fwd(const float* axisangle, const float* translation, float* T, int N, int invert, void* stream);
+int wmd_pose_transform_bwd(const float* axisangle, const float* translation, const float* dT, float* d_axisangle,
+                           float* d_translation, int N, int invert, void* stream);
+
+/* The shared tail of PoseDecoder (pose_decoder.py:43-52) and PoseCNN (pose_cnn.py:42-48): a 1x1 convolution to 6 F
+ * channels, the mean over H x W and the 0.01 scale, evaluated with the mean first:
+ *   params[b, f, :] = scale * (bias + w . mean_hw(x[b]))      x [B,C,H,W], w [6F,C], bias [6F] or NULL, params [B,F,6]
+ * params[b, f, 0:3] is the axis-angle and params[b, f, 3:6] the translation of frame f.  T [B,F,4,4] or NULL: the transform
+ * of every frame as above, frame f inverted when bit f of invert_mask is set.  means [B,C] receives mean_hw(x) for the
+ * backward.  One launch.  F in 1..4 (WMD_ERR_UNSUPPORTED beyond), (C + 24) floats must fit 64 KB of LDS; H W may be 1
+ * and need not be a multiple of 4, C need not be a multiple of 64.                                                       */
+int wmd_pose_head_fwd(const float* x, const float* w, const float* bias, float* params, float* T, float* means, int B, int C,
+                      int H, int W, int F, int invert_mask, float scale, void* stream);
+
+/* Backward of wmd_pose_head_fwd from d_params [B,F,6] and / or dT [B,F,4,4] (either may be NULL, not both), with the
+ * forward's params and means: dx [B,C,H,W], dw [6F,C], dbias [6F] (each may be NULL).  workspace: 6 F B floats.
+ * Two launches; the sums over B run in ascending order without atomics, so two runs give the same bits.              */
+int wmd_pose_head_bwd(const float* params, const float* means, const float* w, const float* d_params, const float* dT,
+                      float* dx, float* dw, float* dbias, float* workspace, int B, int C, int H, int W, int F, int invert_mask,
+                      float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,14 @@
 """Factories with the reference's names, signatures and selection logic
-(/root/reference/KITTI/networks/network_constructors.py): `make_depth_decoder(encoder, opts)` (:30-40) and
-`make_depth_encoder(opts)` (:12-27; the encoders are the plain torch.nn ones of `wavelet_monodepth_amd.encoders`).  The pose factory of that file is out of scope.  Nothing is printed.
+(/root/reference/KITTI/networks/network_constructors.py): `make_depth_decoder(encoder, opts)` (:30-40),
+`make_depth_encoder(opts)` (:12-27; the encoders are the plain torch.nn ones of `wavelet_monodepth_amd.encoders`) and
+`make_posenet(opts, depth_encoder, num_pose_frames, num_input_frames)` (:43-64).  Nothing is printed.
 
 `make_depth_decoder` also accepts the explicit form `make_depth_decoder(num_ch_enc, scales, use_wavelets=..., use_sparse=...)`
 for callers that have no option namespace.
 """
 from .depth_decoder import DepthDecoder, DepthWaveProgressiveDecoder
+from .pose_cnn import PoseCNN
+from .pose_decoder import PoseDecoder
 
 
 def make_depth_encoder(opts):
@@ -34,3 +37,21 @@ def make_depth_decoder(encoder, opts=None, use_wavelets=False, use_sparse=False)
                 else SparseDepthWaveProgressiveDecoder(num_ch_enc, scales)
         return DepthWaveProgressiveDecoder(num_ch_enc, scales)
     return DepthDecoder(num_ch_enc, scales)
+
+
+def make_posenet(opts, depth_encoder, num_pose_frames, num_input_frames):
+    """-> (pose_encoder or None, pose_decoder).  "separate_resnet": a ResNet of its own over `num_pose_frames` stacked images
+    (a PyTorch module, like the depth encoder) and a one-feature PoseDecoder that predicts two frames; "shared": a PoseDecoder
+    over `num_pose_frames` feature lists of the depth encoder; "posecnn": PoseCNN over all frames or a pair."""
+    from ..encoders import ResnetEncoder
+    pose_encoder = None
+    if opts.pose_model_type == "separate_resnet":
+        pose_encoder = ResnetEncoder(opts.num_layers, opts.weights_init == "pretrained", num_input_images=num_pose_frames)
+        pose_decoder = PoseDecoder(pose_encoder.num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
+    elif opts.pose_model_type == "shared":
+        pose_decoder = PoseDecoder(depth_encoder.num_ch_enc, num_pose_frames)
+    elif opts.pose_model_type == "posecnn":
+        pose_decoder = PoseCNN(num_input_frames if opts.pose_model_input == "all" else 2)
+    else:
+        raise NotImplementedError("pose_model_type %r" % (opts.pose_model_type,))
+    return pose_encoder, pose_decoder

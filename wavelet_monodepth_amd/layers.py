@@ -6,10 +6,12 @@ parameter belongs to a Conv2d/Linear) keep working; the holders' own forward is 
   KITTI flavour: Conv3x3(in, out, use_refl=True), Conv1x1, ConvBlock(in, out, kernel_size, use_refl)
                  (KITTI/layers.py:120-173)
   NYUv2 flavour: NyuConv3x3(in, out, padding=...), UpSampleBlock (NYUv2/networks/layers.py:11-32,57-67)
+  pose:          transformation_from_parameters, rot_from_axisangle, get_translation_matrix (KITTI/layers.py:42-117)
 """
 import torch.nn as nn
 
 from . import ops
+from .ops import transformation_from_parameters  # noqa: F401  (the reference keeps it in layers.py)
 
 
 class DeferredActivation:
@@ -179,3 +181,13 @@ class UpSampleBlock(nn.Module):
 
     def forward(self, x, concat_with, x1_gate=None, grad_is_dz=False):
         return self.convA(x, skip=concat_with, up=2, act="leaky", slope=0.2, x1_gate=x1_gate, grad_is_dz=grad_is_dz)
+
+
+def rot_from_axisangle(vec):
+    """An axis-angle rotation [B,1,3] as a 4x4 matrix [B,4,4]: the pose transform with a zero translation."""
+    return ops.transformation_from_parameters(vec, vec.new_zeros(vec.shape))
+
+
+def get_translation_matrix(translation_vector):
+    """A translation [B,1,3] or [B,3] as a 4x4 matrix [B,4,4]: the pose transform with a zero axis-angle."""
+    return ops.transformation_from_parameters(translation_vector.new_zeros(translation_vector.shape), translation_vector)

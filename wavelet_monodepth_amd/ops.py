@@ -8,6 +8,8 @@ Each function mirrors one reference operator group (file:line under /root/refere
                  (depth_decoder.py:104-136; densedepth_decoder.py:106-115)
   idwt_haar      IDWT(wave="haar", mode="zero") + disparity normalisation (depth_decoder.py:164-166)
   dwt_haar       DWT(J, "haar", "reflect") on even sizes (NYUv2/train.py:258,289)
+  pose_head      last 1x1 of the pose networks + spatial mean + 0.01 + the 4x4 transforms (pose_decoder.py:43-52, pose_cnn.py:42-48)
+  transformation_from_parameters   axis-angle + translation -> 4x4 transform (KITTI/layers.py:42-117)
 All of them are differentiable (torch.autograd.Function with hand-written HIP backward kernels).
 """
 import contextlib
@@ -1302,3 +1304,86 @@ def upsample_bilinear(x, size, align_corners=False, depth_range=None):
     _require_gpu(x)
     y, depth = _UpsampleFn.apply(x, int(size[0]), int(size[1]), bool(align_corners), depth_range)
     return (y, depth) if depth_range is not None else y
+
+
+# ---------------------------------------------------------------------------------------------
+# pose path: trunk output -> (axisangle, translation) -> cam_T_cam (csrc/wmd_pose.hip)
+# ---------------------------------------------------------------------------------------------
+
+class _PoseTransformFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, axisangle, translation, invert):
+        v, t = _c(axisangle), _c(translation)
+        N = v.shape[0]
+        T = torch.empty((N, 4, 4), device=v.device, dtype=torch.float32)
+        check(_lib.lib().wmd_pose_transform_fwd(ptr(v), ptr(t), ptr(T), N, int(invert), current_stream()), "wmd_pose_transform_fwd")
+        ctx.save_for_backward(v, t)
+        ctx.invert = int(invert)
+        return T
+
+    @staticmethod
+    def backward(ctx, dT):
+        v, t = ctx.saved_tensors
+        dv, dt = torch.empty_like(v), torch.empty_like(t)
+        check(_lib.lib().wmd_pose_transform_bwd(ptr(v), ptr(t), ptr(_c(dT)), ptr(dv), ptr(dt), v.shape[0], ctx.invert,
+                                                current_stream()), "wmd_pose_transform_bwd")
+        return dv, dt, None
+
+
+def transformation_from_parameters(axisangle, translation, invert=False):
+    """(axisangle, translation) [B,1,3] or [B,3] -> the 4x4 transform [B,4,4] (KITTI/layers.py:42-59), inverted on request:
+    one kernel forward, one backward."""
+    _require_gpu(axisangle, translation)
+    B = axisangle.shape[0]
+    if axisangle.numel() != 3 * B or translation.numel() != 3 * B:
+        raise _lib.WmdError("transformation_from_parameters expects [B,1,3] or [B,3] tensors, got %s and %s"
+                            % (tuple(axisangle.shape), tuple(translation.shape)))
+    return _PoseTransformFn.apply(axisangle.reshape(B, 3), translation.reshape(B, 3), bool(invert))
+
+
+class _PoseHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, frames, invert_mask, scale):
+        x, w, bias = _c(x), _c(weight), _c(bias)
+        B, Cc, H, W = x.shape
+        params = torch.empty((B, frames, 6), device=x.device, dtype=torch.float32)
+        T = torch.empty((B, frames, 4, 4), device=x.device, dtype=torch.float32)
+        means = torch.empty((B, Cc), device=x.device, dtype=torch.float32)
+        check(_lib.lib().wmd_pose_head_fwd(ptr(x), ptr(w), ptr(bias), ptr(params), ptr(T), ptr(means), B, Cc, H, W, frames,
+                                           invert_mask, scale, current_stream()), "wmd_pose_head_fwd")
+        ctx.save_for_backward(params, means, w)
+        ctx.cfg = (tuple(x.shape), tuple(weight.shape), frames, invert_mask, scale, bias is not None)
+        ctx.set_materialize_grads(False)
+        return params, T
+
+    @staticmethod
+    def backward(ctx, d_params, dT):
+        params, means, w = ctx.saved_tensors
+        (B, Cc, H, W), wshape, frames, invert_mask, scale, has_bias = ctx.cfg
+        if d_params is None and dT is None:
+            return (None,) * 6
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        new = lambda *shape: torch.empty(shape, device=w.device, dtype=torch.float32)
+        dx = new(B, Cc, H, W) if need_x else None
+        dw = new(*wshape) if need_w else None
+        db = new(6 * frames) if need_b and has_bias else None
+        ws = new(B * 6 * frames)
+        check(_lib.lib().wmd_pose_head_bwd(ptr(params), ptr(means), ptr(w), ptr(_c(d_params)), ptr(_c(dT)), ptr(dx), ptr(dw), ptr(db),
+                                           ptr(ws), B, Cc, H, W, frames, invert_mask, scale, current_stream()), "wmd_pose_head_bwd")
+        return dx, dw, db, None, None, None
+
+
+def pose_head(x, weight, bias, frames, invert_mask=0, scale=0.01):
+    """The tail both pose networks share (pose_decoder.py:43-52, pose_cnn.py:42-48): scale * mean_hw(conv1x1(x)) as the mean
+    first and the 1x1 filter on the [B,C] means, split into axisangle / translation [B,F,1,3], plus the transform of every frame
+    T [B,F,4,4] (frame f inverted when bit f of invert_mask is set) from the same launch.  x [B,C,H,W], weight [6F,C,1,1] or
+    [6F,C], bias [6F] or None.  One kernel forward, two backward."""
+    _require_gpu(x, weight, bias)
+    frames = int(frames)
+    if x.dim() != 4 or weight.numel() != 6 * frames * x.shape[1] or weight.shape[0] != 6 * frames:
+        raise _lib.WmdError("pose_head: x %s and weight %s do not give %d frames" % (tuple(x.shape), tuple(weight.shape), frames))
+    if bias is not None and bias.numel() != 6 * frames:
+        raise _lib.WmdError("pose_head: bias has %d entries, expected %d" % (bias.numel(), 6 * frames))
+    params, T = _PoseHeadFn.apply(x, weight, bias, frames, int(invert_mask), float(scale))
+    params = params.view(x.shape[0], frames, 1, 6)
+    return params[..., :3], params[..., 3:], T

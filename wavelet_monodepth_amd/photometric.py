@@ -6,6 +6,7 @@ libwmd_hip.so (csrc/wmd_photo.hip).  Names follow the reference:
     warp_frame(color, depth, K, inv_K, T)         BackprojectDepth + Project3D + F.grid_sample(padding_mode="border")
                                                   (KITTI/layers.py:176-229, KITTI/trainer.py:352-372) fused
     get_smooth_loss(disp, img, gamma=2)           KITTI/layers.py:238-252
+    predict_poses(inputs, features, models, opt)  KITTI/trainer.py:254-310: the pose networks -> outputs[("cam_T_cam", 0, f)]
     generate_images_pred / compute_loss_masks / compute_losses   the trainer's orchestration (KITTI/trainer.py:329-560)
 No CPU fallback: CPU tensors raise.
 """
@@ -155,18 +156,63 @@ class LossOptions:
 
     def __init__(self, height=192, width=640, frame_ids=(0, -1, 1), loss_scales=(0, 1, 2, 3), min_depth=0.1, max_depth=100.0,
                  v1_multiscale=False, disable_automasking=False, avg_reprojection=False, no_ssim=False, use_depth_hints=False,
-                 disparity_smoothness=1e-3, scales=(0, 1, 2, 3)):
+                 disparity_smoothness=1e-3, scales=(0, 1, 2, 3), pose_model_type="separate_resnet", pose_model_input="pairs"):
         self.height, self.width = height, width
         self.frame_ids, self.loss_scales = list(frame_ids), list(loss_scales)
         self.scales = list(scales)      # --scales: the normaliser of the total loss (trainer.py:47,557), separate from --loss_scales
         self.min_depth, self.max_depth = min_depth, max_depth
         self.v1_multiscale, self.disable_automasking, self.avg_reprojection = v1_multiscale, disable_automasking, avg_reprojection
         self.no_ssim, self.use_depth_hints, self.disparity_smoothness = no_ssim, use_depth_hints, disparity_smoothness
+        self.pose_model_type, self.pose_model_input = pose_model_type, pose_model_input
+
+
+def predict_poses(inputs, features, models, opt):
+    """trainer.py:254-310: the poses between the target frame and every temporal source frame (the "s" frame has its fixed
+    stereo_T) -> {("axisangle", 0, f), ("translation", 0, f), ("cam_T_cam", 0, f)}.  `models`: "pose" and, for
+    "separate_resnet", "pose_encoder"; `features`: {frame_id: encoder feature list}, read by the "shared" type only.
+    pose_model_input == "pairs" (or two frames in all): one pass of the pose network per source frame on (earlier, later) in temporal order, the
+    transform inverted for f < 0 and taken from the pose head's own launch.  Otherwise all frames go in together, in the
+    order of opt.frame_ids, and frame f's transform is prediction number i (never inverted)."""
+    from . import ops
+    outputs = {}
+    kind = opt.pose_model_type
+    temporal = [f for f in opt.frame_ids if f != "s"]
+    if opt.pose_model_input == "pairs" or len(opt.frame_ids) == 2:    # num_pose_frames == 2 (trainer.py:49,258)
+        pose_feats = {f: features[f] if kind == "shared" else inputs[("color_aug", f, 0)] for f in temporal}
+        for f_i in opt.frame_ids[1:]:
+            if f_i == "s":
+                continue
+            pose_inputs = [pose_feats[f_i], pose_feats[0]] if f_i < 0 else [pose_feats[0], pose_feats[f_i]]
+            if kind == "separate_resnet":
+                pose_inputs = [models["pose_encoder"](torch.cat(pose_inputs, 1))]
+            elif kind == "posecnn":
+                pose_inputs = torch.cat(pose_inputs, 1)
+            axisangle, translation, T = models["pose"].forward_transforms(pose_inputs, invert_mask=1 if f_i < 0 else 0)
+            outputs[("axisangle", 0, f_i)] = axisangle
+            outputs[("translation", 0, f_i)] = translation
+            outputs[("cam_T_cam", 0, f_i)] = T[:, 0]
+    else:
+        if kind in ("separate_resnet", "posecnn"):
+            pose_inputs = torch.cat([inputs[("color_aug", f, 0)] for f in temporal], 1)
+            if kind == "separate_resnet":
+                pose_inputs = [models["pose_encoder"](pose_inputs)]
+        elif kind == "shared":
+            pose_inputs = [features[f] for f in temporal]
+        else:
+            raise NotImplementedError("pose_model_type %r" % (kind,))
+        axisangle, translation, T = models["pose"].forward_transforms(pose_inputs)
+        for i, f_i in enumerate(opt.frame_ids[1:]):
+            if f_i != "s":
+                outputs[("axisangle", 0, f_i)] = axisangle
+                outputs[("translation", 0, f_i)] = translation
+                outputs[("cam_T_cam", 0, f_i)] = T[:, i]
+    return outputs
 
 
 def generate_images_pred(inputs, outputs, opt):
-    """trainer.py:329-392 (pose_model_type != "posecnn"): every ("disp", s) -> full-resolution depth -> the source frames
-    warped into the target view, stored as outputs[("depth", 0, s)] and outputs[("color", frame_id, s)]."""
+    """trainer.py:329-392: every ("disp", s) -> full-resolution depth -> the source frames warped into the target view, stored
+    as outputs[("depth", 0, s)] and outputs[("color", frame_id, s)].  With pose_model_type == "posecnn" the temporal frames'
+    transform is rebuilt per scale from the translation times the mean inverse depth (:354-362)."""
     from . import ops
     for scale in opt.loss_scales:
         disp = outputs[("disp", scale)]
@@ -181,6 +227,10 @@ def generate_images_pred(inputs, outputs, opt):
         outputs[("depth", 0, scale)] = depth
         for frame_id in opt.frame_ids[1:]:
             T = inputs["stereo_T"] if frame_id == "s" else outputs[("cam_T_cam", 0, frame_id)]
+            if getattr(opt, "pose_model_type", None) == "posecnn" and frame_id != "s":
+                mean_inv_depth = (1 / depth).mean(3, True).mean(2, True)
+                T = ops.transformation_from_parameters(outputs[("axisangle", 0, frame_id)][:, 0],
+                                                       outputs[("translation", 0, frame_id)][:, 0] * mean_inv_depth[:, 0], frame_id < 0)
             outputs[("color", frame_id, scale)] = warp_frame(inputs[("color", frame_id, source_scale)], depth,
                                                              inputs[("K", source_scale)], inputs[("inv_K", source_scale)], T)
             if not opt.disable_automasking:
