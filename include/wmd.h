@@ -181,6 +181,12 @@ int wmd_conv_fwd(const wmd_conv_args* args, void* stream);
 /* Suggested workspace size (floats) for wmd_conv_fwd on this problem. */
 size_t wmd_conv_fwd_workspace_floats(const wmd_conv_args* args);
 
+/* What wmd_conv_fwd would run on this problem, given a workspace of any size (host code: no launch, no pointer is
+ * dereferenced): the table index of the chosen configuration (wmd_conv_config_name), or -1 when no entry takes the
+ * problem; *ksplit (may be NULL) receives the number of K slices.  tune_cfg / tune_ksplit are honoured as in wmd_conv_fwd;
+ * with both 0 this is the cost model's own choice (stream captures on a tuner miss, WMD_AUTOTUNE=0).                  */
+int wmd_conv_fwd_plan(const wmd_conv_args* args, int* ksplit);
+
 /* Winograd-domain weight image of a 3x3 filter: U = G g G^T per (out, in) channel pair, in the fragment order of
  * wmd_conv_pack_weights with 16 transformed positions in place of the 9 taps.  dgrad != 0: the transposed / flipped
  * filter of the data-gradient pass.                                                                              */

@@ -171,6 +171,7 @@ SIGNATURES = {
     "wmd_conv_pack_many": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "wmd_conv_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
     "wmd_conv_fwd_workspace_floats": (C.c_size_t, [C.POINTER(ConvArgs)]),
+    "wmd_conv_fwd_plan": (C.c_int, [C.POINTER(ConvArgs), C.POINTER(C.c_int)]),
     "wmd_conv_num_configs": (C.c_int, []),
     "wmd_conv_config_name": (C.c_char_p, [C.c_int]),
     "wmd_conv_bf16_packed_weight_bytes": (C.c_size_t, [C.c_int] * 3),

@@ -368,7 +368,9 @@ struct W32QTile {
     static constexpr int XCH_FLOATS = 4 * 32 * 64;   // the four quarters trade 32 partial outputs per lane
     static constexpr int LDS_FLOATS = 2 * BUF_FLOATS > XCH_FLOATS ? 2 * BUF_FLOATS : XCH_FLOATS;
     static constexpr int TAB_FLOATS = ((PH + PWS + PHL + PWL + 3) / 4) * 4;
-    static_assert(TH % 2 == 0 && TW % 8 == 0, "whole 2x2 tiles; a lane's four consecutive tiles stay in one tile row");
+    // (narrower than W32Tile's TW % 8: the quarter kernel addresses tile slots by tslot / TXB, tslot % TXB and stores the slot pair
+    //  (2 pc, 2 pc + 1) as one 16-byte piece -- TXB even keeps the pair in one tile row and the piece on a 16-byte boundary)
+    static_assert(TH % 2 == 0 && TW % 4 == 0, "whole 2x2 tiles; a stored pair of tile slots stays in one tile row");
     static_assert(NTILES <= 32 && NTILES % 2 == 0, "one tile group");
     static_assert(CK % 4 == 0 && PWS % 2 == 0 && PSF % 2 == 0, "8-byte patch reads");
     static_assert((LDS_FLOATS + TAB_FLOATS) * 4 <= 53 * 1024, "three blocks per CU");

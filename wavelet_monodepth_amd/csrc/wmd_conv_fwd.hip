@@ -1047,8 +1047,12 @@ static bool plan_conv(const wmd_conv_args* g, ConvPlan* plan, bool have_ws, size
             store(ksmax, nchunks);
             break;
         }
-        // MFMA work of a block per chunk (Winograd: 16 positions x 16 tiles)
-        const double block_macs_per_chunk = (double)c.co_block * c.px_cols * c.CK * c.kpos * fam_model_work(c.family);
+        // MFMA work of a block per chunk (Winograd: 16 positions x 16 tiles).  The 32x32x2 families are charged the tile slots a
+        // block EXECUTES -- 32 per tile group, filled or not, inside the map or past its edge -- so a tile that covers a map with
+        // fewer slots costs less (a 6x20 map: one 6x20 quarter block of 32 slots against two 4x32 ones, or one 64-slot two-group
+        // block); the quarter family's four waves span 64 MFMA columns over ONE group, which px_cols would charge twice
+        const int cols = fam_mfma32(c.family) ? c.groups * 32 : c.px_cols;
+        const double block_macs_per_chunk = (double)c.co_block * cols * c.CK * c.kpos * fam_model_work(c.family);
         for (int ks = 1; ks <= 32; ++ks) {
             if (force_ks > 0 ? ks != force_ks : (ks & (ks - 1)) != 0 || ks > 16) continue;  // model: powers of two
             if (ks > 1 && (!have_ws || nchunks < ks)) continue;
@@ -1174,6 +1178,14 @@ extern "C" size_t wmd_conv_fwd_workspace_floats(const wmd_conv_args* g) {
     if (!g || g->B <= 0 || g->Cout <= 0) return 0;
     ConvPlan plan;
     return plan_conv(g, &plan, true, (size_t)-1) ? plan.workspace_floats : 0;
+}
+
+extern "C" int wmd_conv_fwd_plan(const wmd_conv_args* g, int* ksplit) {
+    if (!g || g->B <= 0 || g->Cout <= 0) return -1;
+    ConvPlan plan;
+    if (!plan_conv(g, &plan, true, (size_t)-1)) return -1;
+    if (ksplit) *ksplit = plan.ksplit;
+    return (int)(plan.cfg - kCfgs);
 }
 
 extern "C" int wmd_conv_fwd(const wmd_conv_args* g, void* stream) {
