@@ -739,6 +739,41 @@ int wmd_eval_errors(const float* pred, const float* gt, int B, size_t n_per_imag
  * (:204) fused: r_disp is the raw prediction for the mirrored image.  l_disp, r_disp, out: [B,h,w].              */
 int wmd_flip_postprocess(const float* l_disp, const float* r_disp, float* out, int B, int h, int w, void* stream);
 
+/* Depth-boundary errors of the NYUv2 evaluation: compute_depth_boundary_error (NYUv2/utils.py:122-169), the dbe_acc /
+ * dbe_com columns of NYUv2/evaluate.py:94-107, for B images of H x W in one call; nothing is read back to the host.
+ *
+ * wmd_eval_canny: img [B,H,W] float -> edges_u8 [B,H,W] (0 / 1).  This is the project's own definition of the detector,
+ * modelled on skimage.feature.canny(image, sigma, low, high) with mask=None (agreement with an actual skimage is not
+ * verified); all arithmetic is float64:
+ *   smoothed = G(img) / (G(ones) + 2.220446049250313e-16), G the separable Gaussian of radius int(4 sigma + 0.5) with
+ *              zeros outside the image (scipy.ndimage.gaussian_filter(mode="constant", truncate=4));
+ *   isobel / jsobel = the Sobel derivatives along rows / columns with mirrored borders (d c b a | a b c d);
+ *   mag = hypot(isobel, jsobel); a pixel off the one-pixel border ring with mag >= low survives when both neighbours along
+ *   the gradient, interpolated between the two nearest of the eight neighbours, are <= mag;
+ *   edges = the 8-connected components of the survivors that hold a survivor with mag >= high.
+ * NaN follows IEEE rules: it spreads through the Gaussian and the Sobel window and fails every comparison.
+ *
+ * wmd_eval_dbe: pred [B,H,W] float, edges_gt_u8 [B,H,W] (non-zero = edge), mask_u8 [B,H,W] or NULL (all ones) ->
+ * out2 [B,2] = (dbe_acc, dbe_com) and, unless NULL, edges_est_u8 [B,H,W]:
+ *   p = pred in float64 with 0 -> NaN, p -= nanmin, p /= nanmax (a constant map is NaN everywhere: no edges);
+ *   edges_est = the detector on p with sigma = sqrt(2) and the two thresholds;
+ *   D_gt, D_est = exact Euclidean distances to the nearest edge pixel; F = edges_est (D_gt < 10) mask;
+ *   F empty: (10, 10); else dbe_acc = sum(D_gt F) / sum(F),
+ *   dbe_com = (sum(min(D_gt mask, 10) edges_est) + sum(min(D_est, 10) edges_gt)) / (sum(edges_est) + sum(edges_gt)).
+ *   An image without ground-truth edges scores (NaN, NaN) with an empty edge map.
+ * The sums are integer histograms over the squared distance added in a fixed order: the same input gives the same bits.
+ *
+ * Sizes: H, W >= 3 (WMD_ERR_BAD_SHAPE below); H * 2 * ceil(W / 64) <= 16384 -- the hysteresis keeps two bit planes of an
+ * image in LDS; 480 x 640 needs 9600 -- and a radius of at most 12 taps (sigma <= 3.1): WMD_ERR_UNSUPPORTED beyond, before
+ * any launch.  workspace: wmd_eval_dbe_workspace_bytes(B, H, W) bytes, 8-byte aligned (0 for a bad shape); a short one is
+ * WMD_ERR_WORKSPACE before any HIP call.                                                                            */
+size_t wmd_eval_dbe_workspace_bytes(int B, int H, int W);
+int wmd_eval_canny(const float* img, unsigned char* edges_u8, int B, int H, int W, double sigma, double low, double high,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int wmd_eval_dbe(const float* pred, const unsigned char* edges_gt_u8, const unsigned char* mask_u8, float* out2,
+                 unsigned char* edges_est_u8, int B, int H, int W, double low, double high, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Photometric loss stack of the KITTI trainer, forward and backward
  * ------------------------------------------------------------------ */

@@ -223,6 +223,9 @@ SIGNATURES = {
     "wmd_eval_kitti": (C.c_int, [C.POINTER(EvalKittiArgs), C.c_void_p]),
     "wmd_eval_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     "wmd_flip_postprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "wmd_eval_dbe_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "wmd_eval_canny": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wmd_eval_dbe": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_double] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "wmd_ssim_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_void_p]),
     "wmd_ssim_bwd_workspace_floats": (C.c_size_t, [C.c_int] * 4),
     "wmd_ssim_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),

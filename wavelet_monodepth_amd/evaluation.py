@@ -1,11 +1,15 @@
 """Evaluation arithmetic on the GPU: what KITTI/evaluate_depth.py and NYUv2/utils.py do per
-image in numpy on the host, for whole batches resident in HBM, through libwmd_hip.so (csrc/wmd_eval.hip).
+image in numpy on the host, for whole batches resident in HBM, through libwmd_hip.so (csrc/wmd_eval.hip, csrc/wmd_dbe.hip).
 
     kitti_metrics(pred_disp, gt_depth, ...)      evaluate_depth.py:268-307 + compute_errors (:50-68)
     flip_postprocess(l_disp, r_disp_raw)         evaluate_depth.py:71-79 with the [:, :, ::-1] of :204 fused
     compute_errors(pred, gt)                     evaluate_depth.py:50-68 on prepared arrays
     compute_errors_nyu(pred, gt)                 NYUv2/utils.py:85-98
     nyu_prediction(pred_y, crop)                 NYUv2/utils.py:213-226,247-250
+    compute_depth_boundary_error(edges_gt, pred) NYUv2/utils.py:122-169: the dbe_acc / dbe_com columns of --eval_edges
+    canny(image, sigma, low, high)               the edge detector behind it: this project's definition, modelled on
+                                                 skimage.feature.canny with mask=None (include/wmd.h states it in full;
+                                                 agreement with an actual skimage is not verified)
 No CPU fallback: CPU tensors raise.
 """
 import ctypes as C
@@ -17,6 +21,7 @@ from ._lib import check, current_stream, ptr
 
 KITTI_NAMES = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 NYU_NAMES = ("abs_rel", "rmse", "log_10", "a1", "a2", "a3")
+NYU_EDGE_NAMES = ("dbe_acc", "dbe_com")
 MIN_DEPTH, MAX_DEPTH, STEREO_SCALE_FACTOR = 1e-3, 80.0, 5.4
 
 
@@ -104,3 +109,61 @@ def nyu_prediction(pred_y, crop, border_crop_size=16):
     t = ops.upsample_bilinear(t, (2 * t.shape[2], 2 * t.shape[3]), align_corners=True)
     t = torch.clamp(t, min=0.4, max=10)
     return t[:, 0, crop[0]:crop[1] + 1, crop[2]:crop[3] + 1]
+
+
+def _edge_args(B, H, W, dev):
+    n = _lib.lib().wmd_eval_dbe_workspace_bytes(B, H, W)
+    return torch.empty(max(n, 8) // 8 + 1, device=dev, dtype=torch.float64), n
+
+
+def _u8(t, what, shape):
+    """bool / uint8 / float map, nonzero = set -> contiguous uint8 of 0 / 1"""
+    if not t.is_cuda:
+        raise _lib.WmdError("evaluation runs on the GPU only (got a %s tensor)" % t.device)
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.WmdError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
+    return (t != 0).to(torch.uint8).contiguous()
+
+
+def canny(image, sigma=1.0, low_threshold=0.1, high_threshold=0.2):
+    """image [B,H,W] (or [H,W]) float32 -> bool edge map of the same shape.  Gaussian smoothing with zeros outside the
+    image, Sobel gradients, non-maximum suppression against the interpolated neighbours along the gradient, hysteresis over
+    8-connected components; thresholds are absolute, all arithmetic float64, NaN pixels spread and never become edges.
+    Modelled on skimage.feature.canny(image, sigma, low_threshold, high_threshold) with mask=None; skimage was not at hand
+    when this was written, so the agreement is by construction only."""
+    _gpu(image)
+    img = image.contiguous()
+    if img.dim() == 2:
+        img = img[None]
+    if img.dim() != 3:
+        raise _lib.WmdError("canny expects [B,H,W] or [H,W], got %s" % (tuple(image.shape),))
+    B, H, W = img.shape
+    edges = torch.empty((B, H, W), device=img.device, dtype=torch.uint8)
+    ws, n = _edge_args(B, H, W, img.device)
+    check(_lib.lib().wmd_eval_canny(ptr(img), ptr(edges), B, H, W, float(sigma), float(low_threshold), float(high_threshold),
+                                    ptr(ws), n, current_stream()), "wmd_eval_canny")
+    return edges.bool().view(image.shape)
+
+
+def compute_depth_boundary_error(edges_gt, pred, mask=None, low_thresh=0.15, high_thresh=0.3):
+    """NYUv2/utils.py:122-169 for a batch: pred [B,H,W] float32, edges_gt [B,H,W] (bool, uint8 or float, nonzero = edge),
+    mask [B,H,W] binary or None -> (scores [B,2] float32 in NYU_EDGE_NAMES order, edges_est bool [B,H,W]).
+    The prediction is normalised to 0..1 over its non-zero pixels (zeros become NaN holes), edges_est = canny(sigma=sqrt 2)
+    with the two thresholds, and the scores are the directed (dbe_acc) and the symmetric, truncated (dbe_com) chamfer
+    distances between the two edge maps; (10, 10) when no predicted edge lies within 10 pixels of a ground-truth edge.
+    An image without ground-truth edges scores (nan, nan) with an empty edge map: the reference assigns those values and
+    then fails on an unbound D_est in its return statement (:169).  Deterministic: the same input gives the same bits.
+    The reference is called once per image on the host (NYUv2/utils.py:262-266); this is one call per batch."""
+    _gpu(pred)
+    if pred.dim() != 3:
+        raise _lib.WmdError("compute_depth_boundary_error expects pred [B,H,W], got %s" % (tuple(pred.shape),))
+    pred = pred.contiguous()
+    B, H, W = pred.shape
+    gt = _u8(edges_gt, "edges_gt", pred.shape)
+    m = None if mask is None else _u8(mask, "mask", pred.shape)
+    scores = torch.empty((B, 2), device=pred.device, dtype=torch.float32)
+    edges = torch.empty((B, H, W), device=pred.device, dtype=torch.uint8)
+    ws, n = _edge_args(B, H, W, pred.device)
+    check(_lib.lib().wmd_eval_dbe(ptr(pred), ptr(gt), ptr(m), ptr(scores), ptr(edges), B, H, W, float(low_thresh),
+                                  float(high_thresh), ptr(ws), n, current_stream()), "wmd_eval_dbe")
+    return scores, edges.bool()
