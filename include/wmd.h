@@ -815,6 +815,33 @@ int wmd_smooth_fwd(const float* disp, const float* img, float* out, int B, int C
 int wmd_smooth_bwd(const float* disp, const float* img, const float* grad_out, float* ddisp, int B, int C, int H, int W,
                    float gamma, void* stream);
 
+/* Depth-hint fusion (KITTI/precompute_depth_hints.py:243-249; the disparity conversion of :149): per pixel, the depth of
+ * the candidate whose reprojection of the other stereo view matches the base image best.  One launch, no M-fold copies.
+ * The stereo matcher that produces the candidates is out of scope: they come from the caller.
+ *   cand [B,M,H,W]: depths, or -- cand_is_disparity != 0 -- pixel disparities d, converted as
+ *                   depth = focal_times_baseline / (d + 1e-7f) * (d > 0 ? 1 : 0).  A depth of 0 ("no match") is a legal
+ *                   candidate and takes part in the minimum like any other, as in the reference.
+ *   base, lookup [B,C,H,W] (C in 1..3, base in [0,1]); K, inv_K, T [B,4,4] row-major; T per image (the sign of the
+ *                   baseline differs between a left and a right base image).
+ *   loss(b,m,p) = w_ssim * mean_c clamp((1 - SSIM)/2, 0, 1) + w_l1 * mean_c |base - warped_m|, 3 x 3 windows over a
+ *                   ReflectionPad2d(1) of both images, warped_m = wmd_warp_fwd's arithmetic on lookup with candidate m (the
+ *                   reflected neighbour is the warped value at the reflected pixel, with that pixel's own candidate).
+ *   best_index [B,H,W] (int): the lowest m among the smallest float32 losses (a running minimum with strict <);
+ *   best_depth [B,1,H,W]: that candidate's depth, bit for bit the value that was warped; losses [B,M,H,W] or NULL: the
+ *                   float32 values that were compared.
+ * Refused before any HIP call: a NULL required pointer (WMD_ERR_BAD_ARG); B < 1, M < 1, C < 1, H < 2 or W < 2
+ * (WMD_ERR_BAD_SHAPE); M > WMD_DEPTH_HINTS_MAX_CANDIDATES, C > 3, B > 65535, more than 2^31 elements
+ * (WMD_ERR_UNSUPPORTED); workspace_floats below wmd_depth_hints_workspace_floats(B, M, H, W), or a non-zero
+ * workspace_floats with a NULL workspace (WMD_ERR_WORKSPACE).  The kernel stages nothing in device memory, so the size
+ * asked for is 0 today and NULL / 0 is accepted.  Finite inputs give finite losses (the SSIM denominators are >= C1 C2);
+ * the result for non-finite inputs is undefined (no fault: a NaN sample coordinate reads pixel 0).                        */
+#define WMD_DEPTH_HINTS_MAX_CANDIDATES 64
+size_t wmd_depth_hints_workspace_floats(int B, int M, int H, int W);
+int wmd_depth_hints_fuse(const float* cand, int cand_is_disparity, float focal_times_baseline, const float* base,
+                         const float* lookup, const float* K, const float* inv_K, const float* T, float* best_depth,
+                         int* best_index, float* losses, int B, int M, int C, int H, int W, float eps, float w_ssim, float w_l1,
+                         float* workspace, size_t workspace_floats, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Pose networks: from the pose trunk's last feature map to cam_T_cam, forward and backward
  * ------------------------------------------------------------------ */
