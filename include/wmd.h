@@ -842,6 +842,34 @@ int wmd_depth_hints_fuse(const float* cand, int cand_is_disparity, float focal_t
                          int* best_index, float* losses, int B, int M, int C, int H, int W, float eps, float w_ssim, float w_l1,
                          float* workspace, size_t workspace_floats, void* stream);
 
+/* KITTI ground-truth depth maps from velodyne scans: generate_depth_map (KITTI/kitti_utils.py:52-104) for B scans in one
+ * call, nothing read back to the host.
+ *   points  [total_points,4] float32, the scans packed one after the other in file order (x forward, y left, z up; the 4th
+ *           column is ignored and taken as 1), 16-byte aligned; NULL only with total_points == 0
+ *   offsets [B+1] int64 on the device: scan b is rows offsets[b] .. offsets[b+1]-1.  total_points is the host's length of
+ *           the packed list (the offsets are not read back): no row at or beyond it is read, and a row that no scan claims
+ *           is dropped
+ *   P       [B,3,4] float64 row-major, the reference's P_velo2im per scan;  depth [B,H,W] float32
+ * Per scan, with i the row's index in its scan:
+ *   1. row i is kept iff x >= 0 (true for -0.0, false for NaN);
+ *   2. in float64, every product and sum rounded on its own: p_r = ((P[r,0] x + P[r,1] y) + P[r,2] z) + P[r,3];
+ *      u = rint(p_0 / p_2) - 1, v = rint(p_1 / p_2) - 1 (half to even, IEEE division, p_2 <= 0 not special-cased);
+ *      val = x if vel_depth else p_2;
+ *   3. the row is valid iff u >= 0, v >= 0, u < W and v < H, compared in float64;
+ *   4. depth[v,u] = val of the valid row with the highest i at that pixel, 0 without one;
+ *   5. key = v (W - 1) + u - 1 (the reference's sub2ind): for every key that more than one valid row holds, the pixel of
+ *      that key's lowest-i row receives the minimum val over the key's rows;
+ *   6. values < 0 become 0; val is rounded to float32 once (the minimum commutes with that rounding).
+ * Rules 4 and 5 are resolved by integer atomics on packed (index, value) words: the same input gives the same bits.
+ * The call initialises its workspace itself.  Three launches (two with total_points == 0).
+ * Refused before any HIP call: a NULL offsets, P or depth, a NULL points with total_points > 0 or a misaligned
+ * points (WMD_ERR_BAD_ARG); B, H or W < 1 (WMD_ERR_BAD_SHAPE); H W or total_points -- which bounds every
+ * scan's length -- at or above 2^31 (WMD_ERR_UNSUPPORTED); a workspace that is NULL, not 8-byte aligned or shorter than
+ * wmd_lidar_depth_workspace_bytes(B, H, W) (WMD_ERR_WORKSPACE).  The size query returns 0 for a shape the call refuses. */
+size_t wmd_lidar_depth_workspace_bytes(int B, int H, int W);
+int wmd_lidar_depth_maps(const float* points, const long long* offsets, const double* P, size_t total_points, int B, int H,
+                         int W, int vel_depth, float* depth, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Pose networks: from the pose trunk's last feature map to cam_T_cam, forward and backward
  * ------------------------------------------------------------------ */

@@ -238,6 +238,8 @@ SIGNATURES = {
     "wmd_depth_hints_workspace_floats": (C.c_size_t, [C.c_int] * 4),
     "wmd_depth_hints_fuse": (C.c_int, [C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float] * 3 +
                              [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wmd_lidar_depth_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "wmd_lidar_depth_maps": (C.c_int, [C.c_void_p] * 3 + [C.c_size_t] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wmd_pose_transform_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p]),
     "wmd_pose_transform_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p]),
     "wmd_pose_head_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
