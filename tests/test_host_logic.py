@@ -905,6 +905,114 @@ def test_head_front_end_answers_are_pinned():
     assert dict(zip(_HEAD3X3_WORKSPACE_PINS, ws)) == _HEAD3X3_WORKSPACE_PINS
 
 
+# The route of the stacked heads' backward (ops._head_bwd_route), as the three inline expressions of _stacked_heads_backward answered
+# before they became that function: (case, B*H*W, [(3x3 rows, channels)] of the heads in `mid` order, Ct, low-pass head, gate on x,
+# "own3 own1 merged" as y / n under: the default switches | _HEAD_BWD off | _HEAD_BWD_MERGED off | both pixel thresholds 0).
+# KITTI ResNet18 640x192 at batch 12 and 1; low-pass levels above and below the 1x1 threshold; a gate the 1x1 kernels do not
+# differentiate; Ct % 8 != 0; more than 24 channel slices; a 2-row head.
+_HEAD_BWD_ROUTE_PINS = [
+    ("r18_b12_c32", 368640, [(3, 32), (3, 32)], 64, False, "none", "yyy nnn yyn yyy"),
+    ("r18_b12_c64", 92160, [(3, 64), (3, 64)], 128, False, "elu", "yyy nnn ynn yyy"),
+    ("r18_b12_c128", 23040, [(3, 128), (3, 128)], 256, False, "elu", "yyy nnn ynn yyy"),
+    ("r18_b12_c256_ll", 5760, [(1, 64), (3, 256), (3, 256)], 576, True, "elu", "nnn nnn nnn yyn"),
+    ("r18_b1_c32", 30720, [(3, 32), (3, 32)], 64, False, "none", "yyy nnn ynn yyy"),
+    ("r18_b1_c64", 7680, [(3, 64), (3, 64)], 128, False, "elu", "nnn nnn nnn yyy"),
+    ("r18_b1_c128", 1920, [(3, 128), (3, 128)], 256, False, "elu", "nnn nnn nnn yyy"),
+    ("r18_b1_c256_ll", 480, [(1, 64), (3, 256), (3, 256)], 576, True, "elu", "nnn nnn nnn yyn"),
+    ("ll_196608", 196608, [(1, 64), (3, 256), (3, 256)], 576, True, "elu", "yyn nnn yyn yyn"),
+    ("ll_100000", 100000, [(1, 64), (3, 256), (3, 256)], 576, True, "elu", "ynn nnn ynn yyn"),
+    ("sigmoid_gate_small", 30720, [(3, 32), (3, 32)], 64, False, "sigmoid", "ynn nnn ynn ynn"),
+    ("sigmoid_gate_large", 368640, [(3, 32), (3, 32)], 64, False, "sigmoid", "ynn nnn ynn ynn"),
+    ("ct36", 368640, [(3, 18), (3, 18)], 36, False, "none", "ynn nnn ynn ynn"),
+    ("c1024_slices", 368640, [(3, 1024), (3, 1024)], 2048, False, "none", "nyn nnn nyn nyn"),
+    ("two_row_head", 368640, [(2, 32), (3, 32)], 64, False, "none", "nyn nnn nyn nyn"),
+    ("leaky_gate", 368640, [(3, 32), (3, 32)], 64, False, "leaky", "yyy nnn yyn yyy"),
+]
+_HEAD_BWD_ROUTE_SWITCHES = [{}, {"_HEAD_BWD": False}, {"_HEAD_BWD_MERGED": False}, {"_HEAD_BWD_MIN_PIXELS": 0, "_HEAD_BWD1_MIN_PIXELS": 0}]
+
+
+@pytest.mark.parametrize("column", range(4), ids=["default", "head_bwd_off", "merged_off", "thresholds_0"])
+def test_head_backward_route_table(column, monkeypatch):
+    """Which kernels a level's head backward runs is host arithmetic on the module switches (read at call time: tests and tools
+    assign them) and touches neither a tensor nor the library."""
+    from wavelet_monodepth_amd import ops
+    from wavelet_monodepth_amd._lib import ACT
+    for name, value in {"_HEAD_BWD": True, "_HEAD_BWD_MERGED": True, "_HEAD_BWD_MIN_PIXELS": 16384, "_HEAD_BWD1_MIN_PIXELS": 196608,
+                        **_HEAD_BWD_ROUTE_SWITCHES[column]}.items():
+        monkeypatch.setattr(ops, name, value)
+    for case, pixels, heads, Ct, has_ll, gate, expected in _HEAD_BWD_ROUTE_PINS:
+        route = ops._head_bwd_route(pixels, heads, Ct, has_ll, ACT[gate])
+        want = tuple(c == "y" for c in expected.split()[column])
+        assert tuple(route) == want and (route.own3, route.own1, route.merged) == want, case
+
+
+# The workspace answers and refusals of the heads' backward: (B, H, W, [(row0, nrows, ch0, nch)], Ct, C) -> floats answered by
+# wmd_head3x3_bwd_workspace_floats (for the larger of the two stages' block counts, so that the buffer also serves the fused
+# C = 32 form), floats wmd_head3x3_bwd and the three-launch form of wmd_head_bwd need (the 3x3 stage's own block count), floats
+# answered by wmd_head1x1_bwd_workspace_floats.  One block partial is 2064 / 4160 floats; blocks = ceil(64-pixel tiles / 4),
+# at most 256 / 512.  The first level is admissible for the fused form; the fourth has the low-pass head (no merged call).
+_HEAD_BWD_WORKSPACE_PINS = [
+    ((12, 96, 320, [(0, 3, 0, 32), (3, 3, 32, 32)], 64, 32), 2113536, 1056768, 2129920),
+    ((12, 48, 160, [(0, 3, 0, 64), (3, 3, 64, 64)], 128, 64), 1486080, 1056768, 2995200),
+    ((12, 24, 80, [(0, 3, 0, 128), (3, 3, 128, 128)], 256, 128), 743040, 743040, 2995200),
+    ((2, 6, 20, [(0, 1, 0, 64), (1, 3, 64, 256), (4, 3, 320, 256)], 576, 256), 18576, 18576, 149760),
+    ((1, 8, 8, [(0, 3, 0, 32)], 64, 32), 2064, 2064, 4160),
+]
+_HEAD_BWD_PIN_CHILD = """
+import ctypes as C, json, sys
+from wavelet_monodepth_amd import _lib
+l = _lib.lib()
+out = []
+for (B, H, W, heads, Ct, Cin), _q3, need3, _q1 in json.loads(sys.argv[1]):
+    a3 = _lib.Head3x3BwdArgs(B=B, H=H, W=W, Ct=Ct, n_out=sum(h[1] for h in heads), pad_mode=1, act=2, slope=0.1, dy3=0x1000, mid=0x2000,
+                             dzmid=0x3000, n_heads=len(heads), workspace=None, workspace_floats=0)
+    for i, (row0, nrows, ch0, nch) in enumerate(heads):
+        a3.head[i] = _lib.HeadBwdHead(row0=row0, nrows=nrows, ch0=ch0, nch=nch, w3=0x4000, dw3=0x5000, db3=0x6000)
+    a1 = _lib.Head1x1BwdArgs(B=B, H=H, W=W, C=Cin, Ct=Ct, x_act=1, x_slope=0.0, dz=0x3000, x=0x7000, w1=0x8000, dx=0x9000, dw1=0xa000,
+                             db1=0xb000, workspace=None, workspace_floats=0)
+    q3, q1 = l.wmd_head3x3_bwd_workspace_floats(C.byref(a3)), l.wmd_head1x1_bwd_workspace_floats(C.byref(a1))
+    refused = []          # every call below is one float short: refused before any launch
+    def call(fn, *args):
+        st = fn(*[C.byref(a) for a in args], None)
+        refused.append([st, l.wmd_last_error().decode()])
+    a3.workspace, a3.workspace_floats = 0xc000, need3 - 1
+    a1.workspace, a1.workspace_floats = 0xd000, q1 - 1
+    call(l.wmd_head3x3_bwd, a3)
+    call(l.wmd_head1x1_bwd, a1)
+    if all(h[1] == 3 for h in heads):
+        a1.workspace_floats = q1
+        call(l.wmd_head_bwd, a3, a1)
+        a3.workspace_floats, a1.workspace_floats = q3, q1 - 1
+        call(l.wmd_head_bwd, a3, a1)
+    out.append([q3, q1, refused])
+print(json.dumps(out))
+"""
+
+
+def test_head_backward_workspace_answers_and_refusals_are_pinned():
+    """The two workspace queries of the heads' backward, and the status and text with which wmd_head3x3_bwd, wmd_head1x1_bwd and
+    wmd_head_bwd refuse a workspace one float short of what they need.  At the fused-admissible first level wmd_head_bwd given
+    less than the query's answer runs the three-launch form, so its refusal names that form's (smaller) requirement.  Like
+    test_head_front_end_answers_are_pinned: a child process without the heads' switches in its environment."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in _HEAD_SWITCH_NAMES}
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    out = subprocess.run([sys.executable, "-c", _HEAD_BWD_PIN_CHILD, json.dumps(_HEAD_BWD_WORKSPACE_PINS)], env=env, capture_output=True,
+                         text=True, check=True).stdout
+    for (level, q3, need3, q1), (got3, got1, refused) in zip(_HEAD_BWD_WORKSPACE_PINS, json.loads(out)):
+        assert (got3, got1) == (q3, q1), level
+        want = [[-5, "wmd_head3x3_bwd: workspace %d < %d floats" % (need3 - 1, need3)],
+                [-5, "wmd_head1x1_bwd: workspace %d < %d floats" % (q1 - 1, q1)]]
+        if all(h[1] == 3 for h in level[3]):
+            want += [[-5, "wmd_head_bwd: 3x3 workspace %d < %d floats" % (need3 - 1, need3)],
+                     [-5, "wmd_head_bwd: 1x1 workspace %d < %d floats" % (q1 - 1, q1)]]
+        assert refused == want, level
+
+
 def test_bind_inputs_routes_are_decided_on_the_host():
     """decoder._bound (round 6): the route of a graph-mode forward is host logic -- buffers themselves / a recurring address set /
     copy -- and is decided before anything is launched.  Checked on stand-in tensors that record their copies (no GPU here)."""

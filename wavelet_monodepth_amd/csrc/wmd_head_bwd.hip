@@ -258,7 +258,6 @@ __global__ __launch_bounds__(256) void head3x3_bwd_data_kernel(const HeadBwdK a)
 // 16 g + 4 kq + i of the wave's 64): lane (r16 = l & 15, kq) gathers g of ITS row for four pixels of each 16-pixel group, lane
 // (j, kq) loads mid of channel j for the same pixels (four 16-byte loads when the plane allows).  Accumulators stay in registers
 // over all tiles of the block.
-constexpr int HB_WW = 4;   // wavefronts per block of the weight kernel (256 threads: it also runs as a component of the merged launch)
 template <int NROWS>
 __device__ __forceinline__ void head3x3_bwd_weight_body(const HeadBwdK& a, int bx, int by, int nbx, float* smem) {
     constexpr int KR = NROWS * 9, RT = (KR + 15) / 16;
@@ -883,20 +882,6 @@ __global__ __launch_bounds__(256, 2) void head_bwd_fused32_kernel(const HeadBwdF
     }
 }
 
-int head1x1_blocks(const wmd_head1x1_bwd_args* g);
-int head1x1_validate(const wmd_head1x1_bwd_args* g);
-void head1x1_fill(const wmd_head1x1_bwd_args* g, Head1x1K* a);
-
-static int head_bwd_blocks(const wmd_head3x3_bwd_args* g) {
-    const long tiles = (long)g->B * (((long)g->H * g->W + 63) / 64);
-    return (int)std::max<long>(1, std::min<long>((tiles + HB_WW - 1) / HB_WW, 256));
-}
-// blocks the workspace is sized for: the fused C = 32 launch runs the 1x1 stage's block count (two blocks per CU)
-static int head_bwd_ws_blocks(const wmd_head3x3_bwd_args* g) {
-    const long tiles = (long)g->B * (((long)g->H * g->W + 63) / 64);
-    return std::max(head_bwd_blocks(g), (int)std::max<long>(1, std::min<long>((tiles + H1_WW - 1) / H1_WW, H1_MAX_BLK)));
-}
-
 }  // namespace wmd
 
 using namespace wmd;
@@ -927,80 +912,6 @@ static int head_bwd_validate(const wmd_head3x3_bwd_args* g, int* n_slices) {
     return WMD_OK;
 }
 
-extern "C" size_t wmd_head3x3_bwd_workspace_floats(const wmd_head3x3_bwd_args* g) {
-    int n = 0;
-    if (head_bwd_validate(g, &n)) return 0;
-    return (size_t)head_bwd_ws_blocks(g) * n * HB_PART;
-}
-
-// fills the kernel arguments of the launch set for heads with `nrows` output channels; returns the floats of partials it uses
-static size_t head_bwd_fill(const wmd_head3x3_bwd_args* g, int nrows, int nblk, float* ws, HeadBwdK* a, double* ch_out) {
-    memset(a, 0, sizeof(*a));
-    a->dy3 = g->dy3;
-    a->mid = g->mid;
-    a->dz = g->dzmid;
-    a->B = g->B, a->H = g->H, a->W = g->W, a->Ct = g->Ct, a->n_out = g->n_out, a->pad_mode = g->pad_mode, a->act = g->act;
-    a->slope = g->slope;
-    a->nblk = nblk;
-    double ch = 0;
-    for (int k = 0; k < g->n_heads; ++k) {
-        const wmd_head_bwd_head& h = g->head[k];
-        if (h.nrows != nrows) continue;
-        for (int c0 = 0; c0 < h.nch; c0 += 64) {
-            HeadBwdSlice& sl = a->s[a->n_slices++];
-            sl.row0 = h.row0, sl.ch0 = h.ch0, sl.nch = h.nch, sl.c_begin = c0, sl.c_count = std::min(64, h.nch - c0);
-            sl.w3 = h.w3, sl.dw3 = h.dw3, sl.db3 = h.db3;
-        }
-        ch += h.nch;
-    }
-    a->partial = ws;
-    *ch_out = ch;
-    return (size_t)nblk * a->n_slices * HB_PART;
-}
-
-static int head_bwd_launch_data(const wmd_head3x3_bwd_args* g, const HeadBwdK& a, int nrows, double ch, hipStream_t s) {
-    const double pix = (double)g->B * g->H * g->W;
-    ProfScope prof("head3x3_bwd_data_kernel", 2.0 * 9 * nrows * ch * pix, 4.0 * pix * (2.0 * ch + nrows), s);
-    const long tiles = (long)g->B * (((long)g->H * g->W + 63) / 64);
-    const dim3 dgrid((unsigned)std::max<long>(1, std::min<long>((tiles + 3) / 4, 4096)), a.n_slices);   // one tile per wave
-    if (nrows == 3) hipLaunchKernelGGL(head3x3_bwd_data_kernel<3>, dgrid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(head3x3_bwd_data_kernel<1>, dgrid, dim3(256), 0, s, a);
-    return check_launch("head3x3_bwd_data_kernel");
-}
-
-extern "C" int wmd_head3x3_bwd(const wmd_head3x3_bwd_args* g, void* stream) {
-    int n_all = 0;
-    if (int st = head_bwd_validate(g, &n_all)) return st;
-    const int nblk = head_bwd_blocks(g);
-    if (!g->workspace || g->workspace_floats < (size_t)nblk * n_all * HB_PART)
-        return fail(WMD_ERR_WORKSPACE, "wmd_head3x3_bwd: workspace %zu < %zu floats", g->workspace_floats, (size_t)nblk * n_all * HB_PART);
-    hipStream_t s = (hipStream_t)stream;
-    const double pix = (double)g->B * g->H * g->W;
-    float* ws = g->workspace;
-    for (int nrows = 3; nrows >= 1; nrows -= 2) {   // one launch set per head kind: 3-row (+/-) heads, then the 1-row low-pass head
-        HeadBwdK a;
-        double ch = 0;
-        ws += head_bwd_fill(g, nrows, nblk, ws, &a, &ch);
-        if (a.n_slices == 0) continue;
-        const dim3 grid(nblk, a.n_slices);
-        if (int st = head_bwd_launch_data(g, a, nrows, ch, s)) return st;
-        {
-            ProfScope prof("head3x3_bwd_weight_kernel", 2.0 * 9 * nrows * ch * pix, 4.0 * pix * (ch + nrows), s);
-            if (nrows == 3) hipLaunchKernelGGL(head3x3_bwd_weight_kernel<3>, grid, dim3(HB_WW * 64), 0, s, a);
-            else hipLaunchKernelGGL(head3x3_bwd_weight_kernel<1>, grid, dim3(HB_WW * 64), 0, s, a);
-        }
-        if (int st = check_launch("head3x3_bwd_weight_kernel")) return st;
-        {
-            ProfScope prof("head3x3_bwd_reduce_kernel", (double)nblk * a.n_slices * HB_PART, 4.0 * nblk * a.n_slices * HB_PART, s);
-            const dim3 rgrid(a.n_slices, (9 * nrows * 64 + nrows + 63) / 64);
-            if (nrows == 3) hipLaunchKernelGGL(head3x3_bwd_reduce_kernel<3>, rgrid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL(head3x3_bwd_reduce_kernel<1>, rgrid, dim3(256), 0, s, a);
-        }
-        if (int st = check_launch("head3x3_bwd_reduce_kernel")) return st;
-    }
-    return WMD_OK;
-}
-
 // may both stages run as head_bwd_fused32_kernel?  (two 3-channel heads of 32 channels each over a 32-channel x, whole 64-pixel
 // tiles, rows that are multiples of four pixels; WMD_HEAD_BWD_FUSED=0: never)
 static bool head_bwd_fused_ok(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_bwd_args* a1) {
@@ -1015,6 +926,104 @@ static bool head_bwd_fused_ok(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_
     return a3->H >= 4 && a3->W >= 4 && a3->W % 4 == 0 && HW % 64 == 0;
 }
 
+// floats of the partials of `nblk` blocks over `n_slices` slices
+static size_t head_bwd_partial_floats(int nblk, int n_slices) { return (size_t)nblk * n_slices * HB_PART; }
+
+// Route and launch geometry of the 3x3 stage alone or (a1: its kernel arguments go to h1) of both stages as wmd_head_bwd runs them
+struct HeadBwdPlan {
+    double pix;                     // B H W
+    int n_slices, nblk;             // (head, 64-channel slice) items of all heads; blocks of the 3x3 weight stage or of the fused kernel
+    bool fused;                     // both stages as head_bwd_fused32_kernel
+    size_t need3, need1, query3;    // floats either workspace must hold for this launch; what wmd_head3x3_bwd_workspace_floats answers
+    int data_blocks, nb1d;          // grid.x of head3x3_bwd_data_kernel; blocks of the 1x1 data gradient inside head_bwd_stage2_kernel
+};
+
+static HeadBwdPlan head_bwd_plan(const wmd_head3x3_bwd_args* a3, int n_slices, const wmd_head1x1_bwd_args* a1 = nullptr, Head1x1K* h1 = nullptr) {
+    HeadBwdPlan p = {};
+    const long tiles = head_bwd_tiles(a3->B, a3->H, a3->W);
+    const int nb3 = head3x3_blocks(tiles), nb1 = head1x1_blocks(tiles);
+    p.pix = (double)a3->B * a3->H * a3->W, p.n_slices = n_slices;
+    // the query answers for the larger block count: a buffer sized by it also serves the fused form (the 1x1 stage's count, two blocks per CU)
+    p.query3 = head_bwd_partial_floats(std::max(nb3, nb1), n_slices);
+    // fused only if admissible AND the caller's 3x3 workspace holds the 1x1 block count; else the three-launch form with its own, smaller need
+    p.fused = a1 && head_bwd_fused_ok(a3, a1) && a3->workspace && a3->workspace_floats >= head_bwd_partial_floats(nb1, n_slices);
+    p.nblk = p.fused ? nb1 : nb3;
+    p.need3 = head_bwd_partial_floats(p.nblk, n_slices);
+    p.need1 = a1 ? head1x1_fill(a1, h1) : 0;
+    // the data-gradient cap differs: 4096 blocks for a launch of its own, 1024 as a component of head_bwd_stage2_kernel (one grid.x for all three)
+    p.data_blocks = head_bwd_data_blocks(tiles, HEAD_BWD_DATA_BLK), p.nb1d = head_bwd_data_blocks(tiles, HEAD_BWD_DATA_BLK_MERGED);
+    return p;
+}
+
+extern "C" size_t wmd_head3x3_bwd_workspace_floats(const wmd_head3x3_bwd_args* g) {
+    int n = 0;
+    if (head_bwd_validate(g, &n)) return 0;   // a query on invalid arguments answers 0
+    return head_bwd_plan(g, n).query3;
+}
+
+// fills the kernel arguments of the launch set for heads with `nrows` output channels; returns the mid channels of those heads
+static double head_bwd_fill(const wmd_head3x3_bwd_args* g, int nrows, int nblk, float* ws, HeadBwdK* a) {
+    memset(a, 0, sizeof(*a));
+    a->dy3 = g->dy3, a->mid = g->mid, a->dz = g->dzmid, a->partial = ws;
+    a->B = g->B, a->H = g->H, a->W = g->W, a->Ct = g->Ct, a->n_out = g->n_out, a->pad_mode = g->pad_mode, a->act = g->act;
+    a->slope = g->slope, a->nblk = nblk;
+    double ch = 0;
+    for (int k = 0; k < g->n_heads; ++k) {
+        const wmd_head_bwd_head& h = g->head[k];
+        if (h.nrows != nrows) continue;
+        for (int c0 = 0; c0 < h.nch; c0 += 64) {
+            HeadBwdSlice& sl = a->s[a->n_slices++];
+            sl.row0 = h.row0, sl.ch0 = h.ch0, sl.nch = h.nch, sl.c_begin = c0, sl.c_count = std::min(64, h.nch - c0);
+            sl.w3 = h.w3, sl.dw3 = h.dw3, sl.db3 = h.db3;
+        }
+        ch += h.nch;
+    }
+    return ch;
+}
+
+template <int NROWS>
+static int head_bwd_launch_data(const HeadBwdK& a, const HeadBwdPlan& p, double ch, hipStream_t s) {
+    ProfScope prof("head3x3_bwd_data_kernel", 2.0 * 9 * NROWS * ch * p.pix, 4.0 * p.pix * (2.0 * ch + NROWS), s);
+    hipLaunchKernelGGL(head3x3_bwd_data_kernel<NROWS>, dim3(p.data_blocks, a.n_slices), dim3(256), 0, s, a);
+    return check_launch("head3x3_bwd_data_kernel");
+}
+
+// the three launches of the heads with NROWS output channels: data gradient, weight gradient partials, their reduce
+template <int NROWS>
+static int head_bwd_launch_set(const HeadBwdK& a, const HeadBwdPlan& p, double ch, hipStream_t s) {
+    if (int st = head_bwd_launch_data<NROWS>(a, p, ch, s)) return st;
+    {
+        ProfScope prof("head3x3_bwd_weight_kernel", 2.0 * 9 * NROWS * ch * p.pix, 4.0 * p.pix * (ch + NROWS), s);
+        hipLaunchKernelGGL(head3x3_bwd_weight_kernel<NROWS>, dim3(a.nblk, a.n_slices), dim3(HB_WW * 64), 0, s, a);
+    }
+    if (int st = check_launch("head3x3_bwd_weight_kernel")) return st;
+    {
+        const size_t part = head_bwd_partial_floats(a.nblk, a.n_slices);
+        ProfScope prof("head3x3_bwd_reduce_kernel", (double)part, 4.0 * part, s);
+        hipLaunchKernelGGL(head3x3_bwd_reduce_kernel<NROWS>, dim3(a.n_slices, (9 * NROWS * 64 + NROWS + 63) / 64), dim3(256), 0, s, a);
+    }
+    return check_launch("head3x3_bwd_reduce_kernel");
+}
+
+extern "C" int wmd_head3x3_bwd(const wmd_head3x3_bwd_args* g, void* stream) {
+    int n_all = 0;
+    if (int st = head_bwd_validate(g, &n_all)) return st;
+    const HeadBwdPlan p = head_bwd_plan(g, n_all);
+    // (the 3x3-only size, smaller than the query's answer where the 1x1 stage would run more blocks)
+    if (!g->workspace || g->workspace_floats < p.need3)
+        return fail(WMD_ERR_WORKSPACE, "wmd_head3x3_bwd: workspace %zu < %zu floats", g->workspace_floats, p.need3);
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = g->workspace;
+    for (int nrows = 3; nrows >= 1; nrows -= 2) {   // one launch set per head kind: 3-row (+/-) heads, then the 1-row low-pass head
+        HeadBwdK a;
+        const double ch = head_bwd_fill(g, nrows, p.nblk, ws, &a);
+        if (a.n_slices == 0) continue;
+        ws += head_bwd_partial_floats(p.nblk, a.n_slices);
+        if (int st = nrows == 3 ? head_bwd_launch_set<3>(a, p, ch, s) : head_bwd_launch_set<1>(a, p, ch, s)) return st;
+    }
+    return WMD_OK;
+}
+
 // Both stages of a level's heads in three launches: the 3x3 data gradient (-> dzmid), then the 3x3 weight gradient + the 1x1
 // data gradient + the 1x1 weight gradient as ONE launch, then both reduces as one.  a1->dz must be a3->dzmid.
 // Round 6, C = 32 levels: ONE launch for all four GEMMs (head_bwd_fused32_kernel; dzmid is then not written) + the reduce.
@@ -1026,28 +1035,19 @@ extern "C" int wmd_head_bwd(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_bw
         if (a3->head[k].nrows != 3) return fail(WMD_ERR_UNSUPPORTED, "wmd_head_bwd: 3-channel heads only (the low-pass head: wmd_head3x3_bwd + wmd_head1x1_bwd)");
     if (a1->dz != a3->dzmid || a1->B != a3->B || a1->H != a3->H || a1->W != a3->W || a1->Ct != a3->Ct)
         return fail(WMD_ERR_BAD_ARG, "wmd_head_bwd: the 1x1 stage must consume the 3x3 stage's dzmid (same B, H, W, Ct)");
-    const bool fused = head_bwd_fused_ok(a3, a1) && a3->workspace && a3->workspace_floats >= (size_t)head1x1_blocks(a1) * n_all * HB_PART;
-    const int nblk3 = fused ? head1x1_blocks(a1) : head_bwd_blocks(a3);
-    if (!a3->workspace || a3->workspace_floats < (size_t)nblk3 * n_all * HB_PART)
-        return fail(WMD_ERR_WORKSPACE, "wmd_head_bwd: 3x3 workspace %zu < %zu floats", a3->workspace_floats, (size_t)nblk3 * n_all * HB_PART);
     HeadBwdStage2K m;
     memset(&m, 0, sizeof(m));
-    double ch = 0;
-    head_bwd_fill(a3, 3, nblk3, a3->workspace, &m.h3, &ch);
-    head1x1_fill(a1, &m.h1);
-    const size_t need1 = (size_t)m.h1.nblk * m.h1.n_cgrp * m.h1.n_igrp * H1_PART;
-    if (!a1->workspace || a1->workspace_floats < need1)
-        return fail(WMD_ERR_WORKSPACE, "wmd_head_bwd: 1x1 workspace %zu < %zu floats", a1->workspace_floats, need1);
+    const HeadBwdPlan p = head_bwd_plan(a3, n_all, a1, &m.h1);
+    // (the order of the refusals is part of the contract: the 3x3 workspace first, for the form the plan chose)
+    if (!a3->workspace || a3->workspace_floats < p.need3)
+        return fail(WMD_ERR_WORKSPACE, "wmd_head_bwd: 3x3 workspace %zu < %zu floats", a3->workspace_floats, p.need3);
+    if (!a1->workspace || a1->workspace_floats < p.need1)
+        return fail(WMD_ERR_WORKSPACE, "wmd_head_bwd: 1x1 workspace %zu < %zu floats", a1->workspace_floats, p.need1);
+    const double ch = head_bwd_fill(a3, 3, p.nblk, a3->workspace, &m.h3);
     hipStream_t s = (hipStream_t)stream;
-    const double pix = (double)a3->B * a3->H * a3->W;
-    const long tiles = (long)a3->B * (((long)a3->H * a3->W + 63) / 64);
-    m.n3 = m.h3.n_slices;
-    m.n1d = a1->dx ? m.h1.n_igrp : 0;
-    m.n1w = m.h1.n_cgrp * m.h1.n_igrp;
-    m.nb3 = nblk3;
-    m.nb1d = (int)std::max<long>(1, std::min<long>((tiles + 3) / 4, 1024));
-    m.nb1w = m.h1.nblk;
-    if (fused) {
+    m.n3 = m.h3.n_slices, m.n1d = a1->dx ? m.h1.n_igrp : 0, m.n1w = m.h1.n_cgrp * m.h1.n_igrp;
+    m.nb3 = p.nblk, m.nb1d = p.nb1d, m.nb1w = m.h1.nblk;
+    if (p.fused) {
         HeadBwdFusedK f;
         memset(&f, 0, sizeof(f));
         f.dy3 = a3->dy3, f.mid = a3->mid, f.x = a1->x, f.w1 = a1->w1, f.dx = a1->dx;
@@ -1056,20 +1056,20 @@ extern "C" int wmd_head_bwd(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_bw
         for (int k = 0; k < 2; ++k) f.w3[k] = a3->head[k].w3, f.row0[k] = a3->head[k].row0, f.ch0[k] = a3->head[k].ch0;
         f.m_dslope = a3->act == WMD_ACT_LEAKY ? a3->slope : 1.f, f.m_delu = a3->act == WMD_ACT_ELU ? 1.f : 0.f;
         f.x_dslope = m.h1.dslope, f.x_delu = m.h1.delu;
-        ProfScope prof("head_bwd_fused32_kernel", 2.0 * pix * (2.0 * 27 * 64 + 2.0 * 64 * 32), 4.0 * pix * (64 + 32 + 32 + a3->n_out), s);
-        hipLaunchKernelGGL(head_bwd_fused32_kernel, dim3(nblk3), dim3(256), 0, s, f);
+        ProfScope prof("head_bwd_fused32_kernel", 2.0 * p.pix * (2.0 * 27 * 64 + 2.0 * 64 * 32), 4.0 * p.pix * (64 + 32 + 32 + a3->n_out), s);
+        hipLaunchKernelGGL(head_bwd_fused32_kernel, dim3(p.nblk), dim3(256), 0, s, f);
         if (int st = check_launch("head_bwd_fused32_kernel")) return st;
     } else {
-    if (int st = head_bwd_launch_data(a3, m.h3, 3, ch, s)) return st;
-    {
-        ProfScope prof("head_bwd_stage2_kernel", 2.0 * pix * (27.0 * ch + 2.0 * a1->C * a1->Ct),
-                       4.0 * pix * (ch + 3.0 + 2.0 * a1->Ct + 3.0 * a1->C), s);
-        hipLaunchKernelGGL(head_bwd_stage2_kernel, dim3(std::max(m.nb3, std::max(m.nb1d, m.nb1w)), m.n3 + m.n1d + m.n1w), dim3(256), 0, s, m);
+        if (int st = head_bwd_launch_data<3>(m.h3, p, ch, s)) return st;
+        {
+            ProfScope prof("head_bwd_stage2_kernel", 2.0 * p.pix * (27.0 * ch + 2.0 * a1->C * a1->Ct),
+                           4.0 * p.pix * (ch + 3.0 + 2.0 * a1->Ct + 3.0 * a1->C), s);
+            hipLaunchKernelGGL(head_bwd_stage2_kernel, dim3(std::max(m.nb3, std::max(m.nb1d, m.nb1w)), m.n3 + m.n1d + m.n1w), dim3(256), 0, s, m);
+        }
+        if (int st = check_launch("head_bwd_stage2_kernel")) return st;
     }
-    if (int st = check_launch("head_bwd_stage2_kernel")) return st;
-    }
     {
-        ProfScope prof("head_bwd_reduce2_kernel", (double)nblk3 * m.n3 * HB_PART + (double)need1, 4.0 * (nblk3 * m.n3 * HB_PART + need1), s);
+        ProfScope prof("head_bwd_reduce2_kernel", (double)p.need3 + (double)p.need1, 4.0 * (p.need3 + p.need1), s);
         hipLaunchKernelGGL(head_bwd_reduce2_kernel, dim3(m.n3 + m.n1w, (64 * 64 + 64 + 15) / 16), dim3(256), 0, s, m);
     }
     return check_launch("head_bwd_reduce2_kernel");

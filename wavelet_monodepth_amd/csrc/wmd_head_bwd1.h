@@ -28,6 +28,17 @@ constexpr int H1_WW = 4;                      // wavefronts per block of the wei
 constexpr int H1_MAX_BLK = 512;               // block partials per channel-group pair
 constexpr int H1_PART = 16 * 256 + 64;        // floats of one block's partial: 4 x 4 tiles of 16x16 + 64 bias sums
 constexpr int H1_SMEM_FLOATS = (H1_WW - 1) * 16 * 64 * 4 + H1_WW * 64;   // block reduction of the weight kernel
+constexpr int HB_WW = 4;   // the same of the 3x3 stage (256 threads: it also runs as a component of the merged launch)
+constexpr int HB_MAX_BLK = 256;               // block partials per slice of the 3x3 stage
+
+// ---- launch geometry of both stages (host): a wave owns one 64-pixel tile of one image at a time -----------------------------
+constexpr int HEAD_BWD_DATA_BLK = 4096;          // data-gradient blocks of a launch of its own (wmd_head3x3_bwd, wmd_head1x1_bwd)
+constexpr int HEAD_BWD_DATA_BLK_MERGED = 1024;   // ... of the 1x1 data gradient as a component of head_bwd_stage2_kernel
+inline long head_bwd_tiles(int B, int H, int W) { return (long)B * (((long)H * W + 63) / 64); }
+inline int head_bwd_grid(long tiles, int waves, int cap) { return (int)std::max<long>(1, std::min<long>((tiles + waves - 1) / waves, cap)); }
+inline int head3x3_blocks(long tiles) { return head_bwd_grid(tiles, HB_WW, HB_MAX_BLK); }   // weight stages: blocks of partials
+inline int head1x1_blocks(long tiles) { return head_bwd_grid(tiles, H1_WW, H1_MAX_BLK); }
+inline int head_bwd_data_blocks(long tiles, int cap) { return head_bwd_grid(tiles, 4, cap); }   // one tile per wave of 256 threads
 
 struct Head1x1K {
     const float* dz;
@@ -41,6 +52,11 @@ struct Head1x1K {
     float dslope, delu;     // act'(x) = x > 0 ? 1 : dslope + delu * x
     int nblk, n_cgrp, n_igrp;   // weight kernel: 64-channel groups of dz / of x
 };
+
+// wmd_head_bwd1.hip, for wmd_head_bwd too: the argument checks of the 1x1 stage; its kernel arguments -> the floats of block
+// partials its workspace must hold
+int head1x1_validate(const wmd_head1x1_bwd_args* g);
+size_t head1x1_fill(const wmd_head1x1_bwd_args* g, Head1x1K* a);
 
 // ---- data gradient: D[pixel 16][ci 16] += A[pixel][c] * B[c][ci], A = dz, B = W1 ------------------------------------------
 // grid (pixel tiles, 64-wide groups of ci); a wave owns 64 pixels x <= 4 ci tiles; K = Ct walked four channels per MFMA.

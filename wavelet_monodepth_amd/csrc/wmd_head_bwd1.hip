@@ -23,16 +23,6 @@ __global__ __launch_bounds__(H1_WW * 64) void head1x1_bwd_weight_kernel(const He
 
 __global__ __launch_bounds__(256) void head1x1_bwd_reduce_kernel(const Head1x1K a) { head1x1_bwd_reduce_body(a, blockIdx.x, blockIdx.y, gridDim.x); }
 
-int head1x1_blocks(const wmd_head1x1_bwd_args* g) {
-    const long tiles = (long)g->B * (((long)g->H * g->W + 63) / 64);
-    return (int)std::max<long>(1, std::min<long>((tiles + H1_WW - 1) / H1_WW, H1_MAX_BLK));
-}
-
-}  // namespace wmd
-
-using namespace wmd;
-
-namespace wmd {
 int head1x1_validate(const wmd_head1x1_bwd_args* g) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_head1x1_bwd: null args");
     if (!g->dz || !g->x || !g->w1 || !g->dw1 || !g->db1) return fail(WMD_ERR_BAD_ARG, "wmd_head1x1_bwd: null tensor pointer");
@@ -44,37 +34,40 @@ int head1x1_validate(const wmd_head1x1_bwd_args* g) {
     return WMD_OK;
 }
 
-void head1x1_fill(const wmd_head1x1_bwd_args* g, Head1x1K* a) {
+size_t head1x1_fill(const wmd_head1x1_bwd_args* g, Head1x1K* a) {
     memset(a, 0, sizeof(*a));
     a->dz = g->dz, a->x = g->x, a->w1 = g->w1, a->dx = g->dx, a->dw1 = g->dw1, a->db1 = g->db1;
     a->B = g->B, a->HW = g->H * g->W, a->C = g->C, a->Ct = g->Ct;
     a->dslope = g->x_act == WMD_ACT_LEAKY ? g->x_slope : 1.f;
     a->delu = g->x_act == WMD_ACT_ELU ? 1.f : 0.f;
-    a->nblk = head1x1_blocks(g);
+    a->nblk = head1x1_blocks(head_bwd_tiles(g->B, g->H, g->W));
     a->n_cgrp = (g->Ct + 63) / 64;
     a->n_igrp = (g->C + 63) / 64;
     a->partial = g->workspace;
+    return (size_t)a->nblk * a->n_cgrp * a->n_igrp * H1_PART;
 }
+
 }  // namespace wmd
 
+using namespace wmd;
+
 extern "C" size_t wmd_head1x1_bwd_workspace_floats(const wmd_head1x1_bwd_args* g) {
-    if (head1x1_validate(g)) return 0;
-    return (size_t)head1x1_blocks(g) * ((g->Ct + 63) / 64) * ((g->C + 63) / 64) * H1_PART;
+    if (head1x1_validate(g)) return 0;   // a query on invalid arguments answers 0
+    Head1x1K a;
+    return head1x1_fill(g, &a);
 }
 
 extern "C" int wmd_head1x1_bwd(const wmd_head1x1_bwd_args* g, void* stream) {
     if (int st = head1x1_validate(g)) return st;
     Head1x1K a;
-    head1x1_fill(g, &a);
-    const size_t need = (size_t)a.nblk * a.n_cgrp * a.n_igrp * H1_PART;
+    const size_t need = head1x1_fill(g, &a);
     if (!g->workspace || g->workspace_floats < need)
         return fail(WMD_ERR_WORKSPACE, "wmd_head1x1_bwd: workspace %zu < %zu floats", g->workspace_floats, need);
     hipStream_t s = (hipStream_t)stream;
     const double pix = (double)g->B * g->H * g->W;
-    const long tiles = (long)g->B * (((long)g->H * g->W + 63) / 64);
     if (g->dx) {
         ProfScope prof("head1x1_bwd_data_kernel", 2.0 * g->C * g->Ct * pix, 4.0 * pix * (g->Ct + 2.0 * g->C), s);
-        const dim3 grid((unsigned)std::max<long>(1, std::min<long>((tiles + 3) / 4, 4096)), a.n_igrp);
+        const dim3 grid(head_bwd_data_blocks(head_bwd_tiles(g->B, g->H, g->W), HEAD_BWD_DATA_BLK), a.n_igrp);
         hipLaunchKernelGGL(head1x1_bwd_data_kernel, grid, dim3(256), 0, s, a);
         if (int st = check_launch("head1x1_bwd_data_kernel")) return st;
     }

@@ -12,6 +12,7 @@ Each function mirrors one reference operator group (file:line under /root/refere
   transformation_from_parameters   axis-angle + translation -> 4x4 transform (KITTI/layers.py:42-117)
 All of them are differentiable (torch.autograd.Function with hand-written HIP backward kernels).
 """
+import collections
 import contextlib
 import ctypes as C
 import functools
@@ -704,91 +705,58 @@ class _StackedHeadsFn(torch.autograd.Function):
         return (dx, None, None, None) + tuple(grads)
 
 
-def _heads_bwd_3x3(own, heads, order, offs, rows, dy3, mid, w1s):
-    """3x3 stage of _stacked_heads_backward, on its own kernels (`own`) or on the generic ones: -> ({head: (dw3, db3)}, dzmid =
-    the gradient of `mid` gated by LeakyReLU'(mid), pending, wpd1).  pending: (Head3x3BwdArgs, the tensors it points to) of
-    the own-kernel stage, which the 1x1 stage launches (alone or merged with itself); None when the stage has been launched.
-    wpd1: the data-gradient image of the stacked 1x1 filter w1s (None: not wanted) -- the generic route packs it in the same
-    launch as its own images; otherwise None."""
-    l = _lib.lib()
+_HeadBwdRoute = collections.namedtuple("_HeadBwdRoute", "own3 own1 merged")
+
+
+def _head_bwd_route(pixels, heads, Ct, has_ll, gate_act):
+    """Which kernels run the backward of a level's stacked heads: -> _HeadBwdRoute(own3: the 3x3 stage on wmd_head3x3_bwd, else the
+    generic _dgrad / _wgrad on a block-diagonal filter; own1: the 1x1 stage on wmd_head1x1_bwd, else the generic kernels; merged:
+    both stages as one wmd_head_bwd call).  pixels = B*H*W, heads = [(3x3 output rows, channels)] of every head, Ct = the stacked
+    1x1's output channels, gate_act = the activation code of the caller's gate on x.  Host arithmetic on the module switches only."""
+    nsl = sum((c + 63) // 64 for _r, c in heads)
+    # (worth it where a level has pixels to spread: >= 256 wave tiles; the coarsest level stays on the generic kernels, which
+    # split its few pixels over channels instead -- tools/head_bwd_microbench.py)
+    own3 = bool(_HEAD_BWD and nsl <= 24 and pixels >= _HEAD_BWD_MIN_PIXELS and all(r in (1, 3) for r, _c in heads))
+    # (alone the 1x1 kernels only win at the finest level; as components of the merged second-stage launch -- a level without
+    # the low-pass head whose 3x3 stage runs on its own kernels too -- wherever those do)
+    mergeable = bool(own3 and not has_ll and _HEAD_BWD_MERGED)
+    own1 = bool(_HEAD_BWD and pixels >= (_HEAD_BWD_MIN_PIXELS if mergeable else _HEAD_BWD1_MIN_PIXELS) and Ct % 8 == 0 and
+                gate_act in (ACT["none"], ACT["leaky"], ACT["elu"]))
+    return _HeadBwdRoute(own3, own1, mergeable and own1)
+
+
+def _head3x3_bwd_args(heads, order, offs, rows, dy3, mid, dzmid):
+    """The argument block of wmd_head3x3_bwd / wmd_head_bwd (wmd_head_bwd.hip: tap-partial rows gathered from dy3, one pass over mid
+    each for the data gradient and for the weight + bias gradients of every head) -> (args, {head: (dw3, db3)}, tensors to hold)."""
     B, Ct, H, W = mid.shape
-    n_out, dev = dy3.shape[1], mid.device
-    dzmid = torch.empty_like(mid)
-    if own:
-        # wmd_head_bwd.hip: tap-partial rows gathered from dy3, one pass over mid each for the data gradient and for the weight
-        # + bias gradients of every head
-        dw3s = {k: torch.empty_like(heads[k][2]) for k in order}
-        db3s = {k: torch.empty(heads[k][2].shape[0], device=dev, dtype=torch.float32) for k in order}
-        a = _lib.Head3x3BwdArgs(B=B, H=H, W=W, Ct=Ct, n_out=n_out, pad_mode=PAD["reflect"], act=ACT["leaky"], slope=0.1,
-                                dy3=ptr(dy3), mid=ptr(mid), dzmid=ptr(dzmid), n_heads=len(order), workspace=None,
-                                workspace_floats=0)
-        keep = []
-        for i, k in enumerate(order):
-            w3c = _c(heads[k][2].detach())
-            keep.append(w3c)
-            a.head[i] = _lib.HeadBwdHead(row0=rows[k], nrows=w3c.shape[0], ch0=offs[k], nch=w3c.shape[1], w3=ptr(w3c),
-                                         dw3=ptr(dw3s[k]), db3=ptr(db3s[k]))
-        keep.append(_attach_ws(a, l.wmd_head3x3_bwd_workspace_floats, dev, True))
-        return {k: (dw3s[k], db3s[k]) for k in order}, dzmid, (a, keep), None
-    # the heads as ONE convolution with a block-diagonal filter [n_out, Ct, 3, 3]
-    w3bd = torch.zeros((n_out, Ct, 3, 3), device=dev, dtype=torch.float32)
-    blocks = {k: (slice(rows[k], rows[k] + heads[k][2].shape[0]), slice(offs[k], offs[k] + heads[k][2].shape[1])) for k in order}
-    for k in order:
-        w3bd[blocks[k]] = heads[k][2].detach()
-    # its weight gradient (the diagonal blocks are the heads' gradients) ...
-    dw3f = torch.empty_like(w3bd)
-    db3f = torch.empty(n_out, device=dev, dtype=torch.float32)
-    _wgrad(dy3, mid, None, dw3f, db3f, 3, "reflect", 1)
-    # ... and data gradient; the three weight images of this backward (3x3 data gradient direct + Winograd, 1x1 data gradient)
-    # come from one launch
-    imgs = pack_many([(w3bd, ("dgrad", "wino_dgrad") if _WINOGRAD else ("dgrad",))] + ([(w1s, ("dgrad",))] if w1s is not None else []))
-    _dgrad(dy3, imgs[0]["dgrad"], imgs[0].get("wino_dgrad"), mid, None, dzmid, None, 3, "reflect", 1, ("leaky", 0.1))
-    return ({k: (dw3f[blocks[k]], db3f[blocks[k][0]]) for k in order}, dzmid, None,
-            imgs[1]["dgrad"] if w1s is not None else None)
+    a = _lib.Head3x3BwdArgs(B=B, H=H, W=W, Ct=Ct, n_out=dy3.shape[1], pad_mode=PAD["reflect"], act=ACT["leaky"], slope=0.1,
+                            dy3=ptr(dy3), mid=ptr(mid), dzmid=ptr(dzmid), n_heads=len(order), workspace=None, workspace_floats=0)
+    grads3, keep = {}, []
+    for i, k in enumerate(order):
+        w3c = _c(heads[k][2].detach())
+        grads3[k] = (torch.empty_like(heads[k][2]), torch.empty(w3c.shape[0], device=mid.device, dtype=torch.float32))
+        a.head[i] = _lib.HeadBwdHead(row0=rows[k], nrows=w3c.shape[0], ch0=offs[k], nch=w3c.shape[1], w3=ptr(w3c),
+                                     dw3=ptr(grads3[k][0]), db3=ptr(grads3[k][1]))
+        keep.append(w3c)
+    keep.append(_attach_ws(a, _lib.lib().wmd_head3x3_bwd_workspace_floats, mid.device, True))
+    return a, grads3, keep
 
 
-def _heads_bwd_1x1(own, merged, pending, x, w1s, dzmid, x_gate, want_dx, wpd1):
-    """1x1 stage of _stacked_heads_backward, after (or, `merged`, in the launches of) the pending 3x3 stage: -> (dx or None, the
-    stacked dw1 [Ct,C,1,1], db1 [Ct]).  dx is gated by the caller's activation x_gate if x has one."""
-    l = _lib.lib()
-    B, C_in, H, W = x.shape
-    Ct, dev = w1s.shape[0], x.device
-    dw1f = torch.empty_like(w1s)
-    db1f = torch.empty(Ct, device=dev, dtype=torch.float32)
-    dx = torch.empty_like(x) if want_dx else None
-
-    def launch_pending():
-        if pending is not None:
-            check(l.wmd_head3x3_bwd(C.byref(pending[0]), current_stream()), "wmd_head3x3_bwd")
-
-    if own:
-        # wmd_head_bwd1.hip: one pass over dz and x each for dx and for the stacked weight + bias gradient
-        gate_act, gate_slope = _gate(x_gate)
-        w1c = _c(w1s.reshape(Ct, C_in))
-        a = _lib.Head1x1BwdArgs(B=B, H=H, W=W, C=C_in, Ct=Ct, x_act=gate_act, x_slope=gate_slope, dz=ptr(dzmid), x=ptr(x),
-                                w1=ptr(w1c), dx=ptr(dx), dw1=ptr(dw1f), db1=ptr(db1f), workspace=None, workspace_floats=0)
-        ws1 = _attach_ws(a, l.wmd_head1x1_bwd_workspace_floats, dev, True)
-        if merged:
-            # three launches for both stages: 3x3 data gradient, then [3x3 weights | 1x1 data | 1x1 weights] as one, then
-            # both reduces as one
-            check(l.wmd_head_bwd(C.byref(pending[0]), C.byref(a), current_stream()), "wmd_head_bwd")
-        else:
-            launch_pending()
-            check(l.wmd_head1x1_bwd(C.byref(a), current_stream()), "wmd_head1x1_bwd")
-    else:
-        launch_pending()
-        # weight gradient of the stacked filter and data gradient (one GEMM over all heads' mid channels)
-        _wgrad(dzmid, x, None, dw1f, db1f, 1, "zero", 1)
-        if want_dx:
-            if wpd1 is None:
-                wpd1 = pack_many([(w1s, ("dgrad",))])[0]["dgrad"]
-            _dgrad(dzmid, wpd1, None, x, None, dx, None, 1, "zero", 1, x_gate)
-    return dx, dw1f, db1f
+def _head1x1_bwd_args(x, w1s, dzmid, x_gate, dx, dw1f, db1f):
+    """The argument block of wmd_head1x1_bwd / wmd_head_bwd (wmd_head_bwd1.hip: one pass over dz and x each for dx and for the
+    stacked weight + bias gradient) -> (args, tensors to hold)."""
+    (B, C_in, H, W), Ct = x.shape, w1s.shape[0]
+    gate_act, gate_slope = _gate(x_gate)
+    w1c = _c(w1s.reshape(Ct, C_in))
+    a = _lib.Head1x1BwdArgs(B=B, H=H, W=W, C=C_in, Ct=Ct, x_act=gate_act, x_slope=gate_slope, dz=ptr(dzmid), x=ptr(x),
+                            w1=ptr(w1c), dx=ptr(dx), dw1=ptr(dw1f), db1=ptr(db1f), workspace=None, workspace_floats=0)
+    return a, [w1c, _attach_ws(a, _lib.lib().wmd_head1x1_bwd_workspace_floats, x.device, True)]
 
 
 def _stacked_heads_backward(x, mid, sp, sn, sl, params, meta, d_yh, d_yl, want_dx):
     """Backward of a level's stacked heads from the saved 1x1 outputs `mid` and sigmoid outputs sp / sn / sl (see
     _StackedHeadsFn): -> (dx, [dw1, db1, dw3, db3 of the + head, the - head(, the LL head)])."""
+    l = _lib.lib()
     x_gate, s_hf, s_ll = meta
     heads, has_ll, order, offs, rows = _heads_layout(params)
     B, Ct, H, W = mid.shape
@@ -800,18 +768,47 @@ def _stacked_heads_backward(x, mid, sp, sn, sl, params, meta, d_yh, d_yl, want_d
     parts.append(d_yh * sp * (1.0 - sp) * s_hf)
     parts.append(d_yh * sn * (1.0 - sn) * (-s_hf))
     dy3 = torch.cat(parts, 1)
+    n_out = dy3.shape[1]
     w1s = torch.cat([heads[k][0].detach() for k in order], 0)
-    nsl = sum((heads[k][2].shape[1] + 63) // 64 for k in order)
-    # (worth it where a level has pixels to spread: >= 256 wave tiles; the coarsest level stays on the generic kernels, which
-    # split its few pixels over channels instead -- tools/head_bwd_microbench.py)
-    own3 = _HEAD_BWD and nsl <= 24 and B * H * W >= _HEAD_BWD_MIN_PIXELS and all(heads[k][2].shape[0] in (1, 3) for k in order)
-    grads3, dzmid, pending, wpd1 = _heads_bwd_3x3(own3, heads, order, offs, rows, dy3, mid, w1s if want_dx else None)
-    # (alone the 1x1 kernels only win at the finest level; as components of the merged second-stage launch -- a level without
-    # the low-pass head whose 3x3 stage runs on its own kernels too -- wherever those do)
-    merged = pending is not None and not has_ll and _HEAD_BWD_MERGED
-    own1 = _HEAD_BWD and B * H * W >= (_HEAD_BWD_MIN_PIXELS if merged else _HEAD_BWD1_MIN_PIXELS) and Ct % 8 == 0 and \
-        _gate(x_gate)[0] in (ACT["none"], ACT["leaky"], ACT["elu"])
-    dx, dw1f, db1f = _heads_bwd_1x1(own1, merged, pending, x, w1s, dzmid, x_gate, want_dx, wpd1)
+    route = _head_bwd_route(B * H * W, [tuple(heads[k][2].shape[:2]) for k in order], Ct, has_ll, _gate(x_gate)[0])
+    # dzmid = the gradient of `mid` gated by LeakyReLU'(mid); the stacked dw1 [Ct,C,1,1], db1 [Ct]; dx, gated by x_gate if x has one
+    dzmid = torch.empty_like(mid)
+    dw1f = torch.empty_like(w1s)
+    db1f = torch.empty(Ct, device=mid.device, dtype=torch.float32)
+    dx = torch.empty_like(x) if want_dx else None
+    if route.own3:
+        a3, grads3, _keep3 = _head3x3_bwd_args(heads, order, offs, rows, dy3, mid, dzmid)
+    if route.own1:
+        a1, _keep1 = _head1x1_bwd_args(x, w1s, dzmid, x_gate, dx, dw1f, db1f)
+    imgs = None
+    if route.merged:
+        # three launches for both stages: 3x3 data gradient, [3x3 weights | 1x1 data | 1x1 weights] as one, both reduces as one
+        check(l.wmd_head_bwd(C.byref(a3), C.byref(a1), current_stream()), "wmd_head_bwd")
+    elif route.own3:
+        check(l.wmd_head3x3_bwd(C.byref(a3), current_stream()), "wmd_head3x3_bwd")
+    else:
+        # the heads as ONE convolution with a block-diagonal filter [n_out, Ct, 3, 3]
+        w3bd = torch.zeros((n_out, Ct, 3, 3), device=mid.device, dtype=torch.float32)
+        blocks = {k: (slice(rows[k], rows[k] + heads[k][2].shape[0]), slice(offs[k], offs[k] + heads[k][2].shape[1])) for k in order}
+        for k in order:
+            w3bd[blocks[k]] = heads[k][2].detach()
+        # its weight gradient (the diagonal blocks are the heads' gradients) ...
+        dw3f = torch.empty_like(w3bd)
+        db3f = torch.empty(n_out, device=mid.device, dtype=torch.float32)
+        _wgrad(dy3, mid, None, dw3f, db3f, 3, "reflect", 1)
+        # ... and data gradient; the three weight images of this backward (3x3 data gradient direct + Winograd, 1x1 data gradient)
+        # come from one launch
+        imgs = pack_many([(w3bd, ("dgrad", "wino_dgrad") if _WINOGRAD else ("dgrad",))] + ([(w1s, ("dgrad",))] if want_dx else []))
+        _dgrad(dy3, imgs[0]["dgrad"], imgs[0].get("wino_dgrad"), mid, None, dzmid, None, 3, "reflect", 1, ("leaky", 0.1))
+        grads3 = {k: (dw3f[blocks[k]], db3f[blocks[k][0]]) for k in order}
+    if route.own1 and not route.merged:
+        check(l.wmd_head1x1_bwd(C.byref(a1), current_stream()), "wmd_head1x1_bwd")
+    elif not route.own1:
+        # weight gradient of the stacked filter and data gradient (one GEMM over all heads' mid channels)
+        _wgrad(dzmid, x, None, dw1f, db1f, 1, "zero", 1)
+        if want_dx:
+            wpd1 = (imgs[1] if imgs else pack_many([(w1s, ("dgrad",))])[0])["dgrad"]     # (packed with the generic 3x3 stage's)
+            _dgrad(dzmid, wpd1, None, x, None, dx, None, 1, "zero", 1, x_gate)
     grads = []
     for k, (w1, _b1, _w3, _b3) in enumerate(heads):
         c1 = w1.shape[0]
