@@ -870,6 +870,53 @@ size_t wmd_lidar_depth_workspace_bytes(int B, int H, int W);
 int wmd_lidar_depth_maps(const float* points, const long long* offsets, const double* P, size_t total_points, int B, int H,
                          int W, int vel_depth, float* depth, void* workspace, size_t workspace_bytes, void* stream);
 
+/* KITTI training inputs: MonoDataset.preprocess (KITTI/datasets/mono_dataset.py:118-145) for N decoded frames in one call,
+ * bit for bit what the reference's chain gives over Pillow 12.2: flip, 8-bit Lanczos resize, ToTensor, ColorJitter.
+ *
+ * Tables (host only, no HIP call).  Per axis, scale = in / out, fs = max(scale, 1), support = 3 fs,
+ * ksize = ceil(support) 2 + 1 -- wmd_lanczos_ksize, 0 unless 1 <= in, out <= 32768.  Per output index xx:
+ * center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), in) - xmin,
+ * w[x] = L((x + xmin - center + 0.5) (1 / fs)) with L(t) = sinc(t) sinc(t / 3) on -3 <= t < 3 (libm sin, double), divided by
+ * their sum, k[x] = (int)(w 2^22 +- 0.5).  wmd_lanczos_table writes bounds [out][2] = (xmin, n) and coeffs [out][ksize], zero
+ * beyond n; ksize must be wmd_lanczos_ksize(in, out).  wmd_color_pyramid_tables writes the tables of a whole pyramid, level
+ * after level as (bounds, coeffs) of the width then of the height, wmd_color_pyramid_table_ints ints in all (0 for a shape
+ * the pyramid refuses); the caller uploads them once per shape and passes the device copy as `tables`.
+ *
+ * wmd_color_pyramid.  frames [N,H0,W0,3] uint8 (HWC).  Level s in 0 .. num_scales-1 is h x w = (height >> s) x (width >> s),
+ * resized from the uint8 level s-1 (level 0 from the frame): horizontal pass, uint8 intermediate, vertical pass, each
+ * clip8(((1 << 21) + sum k[x] pix[xmin + x]) >> 22) in int32; an axis whose size does not change is copied.  flip [N] uint8 or
+ * NULL: where set the frame is mirrored before level 0 (a mirrored gather in the first horizontal pass).  The three outputs
+ * hold the levels one after the other, level s at pixel offset N (h_0 w_0 + .. + h_{s-1} w_{s-1}): levels uint8 [N,h,w,3],
+ * color and color_aug float32 [N,3,h,w] = u8 / 255 (a float32 division).  enable [N] uint8, order [N,4] uint8 (a permutation
+ * of 0 brightness, 1 contrast, 2 saturation, 3 hue; read & 3), factors [N,3] float32 (brightness, contrast, saturation),
+ * hue_shift [N] int32 (read & 255), all on the device; enable == NULL: no jitter, color_aug may be NULL and is not written.
+ * Where enable[n] is 0 color_aug equals color.  Otherwise each level's uint8 image goes through the four ops in order, each
+ * uint8 -> uint8: blend(deg, img, f) = trunc(deg + f (img - deg)) in float32, product and sum rounded apart, clamped to
+ * [0, 255] first unless 0 <= f <= 1; brightness deg = 0; saturation deg = grey = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;
+ * contrast deg = (2 sum grey + n) / (2 n) over the n pixels of that image as it enters the op; hue = Pillow's RGB -> HSV,
+ * H = (H + hue_shift) & 255, HSV -> RGB.  The grey sums are 64-bit integer atomics: the same input gives the same bits.
+ * Launches: one per level, one for ToTensor + jitter over all levels, and a memset of the workspace with jitter.
+ * Refused before any HIP call: a NULL frames, tables, levels or color, jitter arrays given in part, enable without
+ * color_aug (WMD_ERR_BAD_ARG); N, a size or num_scales < 1, num_scales > 8 or an empty last level (WMD_ERR_BAD_SHAPE); a
+ * size above 32768, N above 65535 or a ratio whose row footprint does not fit the LDS (WMD_ERR_UNSUPPORTED); a workspace that
+ * is NULL, not 8-byte aligned or shorter than wmd_color_pyramid_workspace_bytes (WMD_ERR_WORKSPACE; 0 for a refused shape).
+ *
+ * wmd_color_jitter: the jitter alone, images [N,h,w,3] uint8 -> out (same layout), a memset and two launches (grey sums, then the chain).
+ * h w < 2^31.  wmd_color_jitter_workspace_bytes(N, h, w) = 8 N, 0 for a refused shape. */
+int wmd_lanczos_ksize(int in, int out);
+int wmd_lanczos_table(int in, int out, int* bounds, int* coeffs, int ksize);
+size_t wmd_color_pyramid_table_ints(int H0, int W0, int height, int width, int num_scales);
+int wmd_color_pyramid_tables(int H0, int W0, int height, int width, int num_scales, int* tables, size_t table_ints);
+size_t wmd_color_pyramid_workspace_bytes(int N, int H0, int W0, int height, int width, int num_scales);
+int wmd_color_pyramid(const unsigned char* frames, int N, int H0, int W0, int height, int width, int num_scales,
+                      const unsigned char* flip, const unsigned char* enable, const unsigned char* order, const float* factors,
+                      const int* hue_shift, const int* tables, unsigned char* levels, float* color, float* color_aug,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t wmd_color_jitter_workspace_bytes(int N, int h, int w);
+int wmd_color_jitter(const unsigned char* images, unsigned char* out, int N, int h, int w, const unsigned char* enable,
+                     const unsigned char* order, const float* factors, const int* hue_shift, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ------------------------------------------------------------------ *
  * Pose networks: from the pose trunk's last feature map to cam_T_cam, forward and backward
  * ------------------------------------------------------------------ */
