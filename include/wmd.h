@@ -917,6 +917,49 @@ int wmd_color_jitter(const unsigned char* images, unsigned char* out, int N, int
                      const unsigned char* order, const float* factors, const int* hue_shift, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* NYUv2 training inputs: getDefaultTrainTransform / getNoTransform (NYUv2/data.py:22-68, :107-140, :199-214) and DepthNorm
+ * (NYUv2/train.py:281) for B decoded samples in one call and ONE launch, bit for bit what the reference's chain gives over
+ * Pillow 12.2: flip, channel swap, the gamma table, crop, 8-bit bicubic resize, ToTensor, * 1000 and the clamp.
+ *
+ * Tables (host only, no HIP call).  wmd_resample_ksize / wmd_resample_table are wmd_lanczos_ksize / wmd_lanczos_table with a
+ * filter argument: support s = 2 for WMD_FILTER_BICUBIC, f(t) = ((a + 2) |t| - (a + 3)) t^2 + 1 for |t| < 1,
+ * (((|t| - 5) |t| + 8) |t| - 4) a for |t| < 2, a = -0.5; s = 3 and L(t) as above for WMD_FILTER_LANCZOS.  Everything else is
+ * the rule stated there with `3` replaced by s: ksize = ceil(s fs) 2 + 1, the bounds, the normalisation and the
+ * (int)(w 2^22 +- 0.5) rounding, in double.  bounds [out][2] = (xmin, n), coeffs [out][ksize], zero beyond n.  Refused: a
+ * NULL pointer, a filter that is neither, a ksize that is not wmd_resample_ksize's (WMD_ERR_BAD_ARG); in or out outside
+ * 1..32768 (WMD_ERR_BAD_SHAPE; wmd_resample_ksize returns 0 for both).
+ * wmd_nyu_inputs_tables writes the four bicubic tables of one call into `tables`, as (bounds, coeffs) of: image width
+ * (W0 - 2 crop -> iw), image height (H0 - 2 crop -> ih), depth width (-> dw), depth height (-> dh);
+ * wmd_nyu_inputs_table_ints ints in all (0 for a shape the call refuses).  The caller uploads them once per shape and passes
+ * the device copy and its length.
+ *
+ * wmd_nyu_inputs.  image_u8 [B,H0,W0,3] and depth_u8 [B,H0,W0] uint8 on the device.  Per item b, in the reference's order:
+ *   flip [B] uint8 or NULL: where set, image and depth are mirrored left-right (a mirrored source column);
+ *   perm [B] uint8 or NULL: index into itertools.permutations(range(3)) = 012, 021, 102, 120, 201, 210 (read clamped to 5):
+ *     image[..., k] = image[..., perm[k]];
+ *   lut [B,256] uint8 or NULL: image = lut[b][image], every channel (the reference's gamma, built by the caller);
+ *   the crop box (crop, crop, W0 - crop, H0 - crop) of both;
+ *   resize of the image to ih x iw and of the depth map to dh x dw: horizontal pass, uint8 intermediate, vertical pass, each
+ *     clip8(((1 << 21) + sum k[x] pix[xmin + x]) >> 22) in int32; an axis whose size does not change is copied;
+ *   image [B,3,ih,iw] float32 = u8 / 255 (a float32 division); depth [B,1,dh,dw] float32 =
+ *     min(max((u8 / 255) * 1000, 10), 1000), every operation rounded on its own; disp_gt (same shape) or NULL = 10 / depth;
+ *   image_resized [B,ih,iw,3] and depth_resized [B,dh,dw] uint8 or NULL: the resized planes in front of the conversion.
+ * A block owns 64 x th output pixels of one image or one depth map and stages their source footprint in LDS; th (at most 16)
+ * is the largest power of two whose footprint, intermediate and coefficients fit 48 KiB.
+ * Refused before any HIP call: a NULL image_u8, depth_u8, tables, image or depth, a misaligned tables, a table_ints that is
+ * not wmd_nyu_inputs_table_ints of the shape (WMD_ERR_BAD_ARG); B or a size < 1, crop < 0, 2 crop >= H0 or 2 crop >= W0
+ * (WMD_ERR_BAD_SHAPE); a size above 32768, B above 65535, or a ratio at which one output row's footprint does not fit the
+ * LDS (WMD_ERR_UNSUPPORTED). */
+typedef enum { WMD_FILTER_BICUBIC = 0, WMD_FILTER_LANCZOS = 1 } wmd_filter;
+int wmd_resample_ksize(int filter, int in, int out);
+int wmd_resample_table(int filter, int in, int out, int* bounds, int* coeffs, int ksize);
+size_t wmd_nyu_inputs_table_ints(int H0, int W0, int crop, int ih, int iw, int dh, int dw);
+int wmd_nyu_inputs_tables(int H0, int W0, int crop, int ih, int iw, int dh, int dw, int* tables, size_t table_ints);
+int wmd_nyu_inputs(const unsigned char* image_u8, const unsigned char* depth_u8, int B, int H0, int W0, int crop, int ih, int iw,
+                   int dh, int dw, const unsigned char* flip, const unsigned char* perm, const unsigned char* lut,
+                   const int* tables, size_t table_ints, float* image, float* depth, float* disp_gt,
+                   unsigned char* image_resized, unsigned char* depth_resized, void* stream);
+
 /* ------------------------------------------------------------------ *
  * Pose networks: from the pose trunk's last feature map to cam_T_cam, forward and backward
  * ------------------------------------------------------------------ */
