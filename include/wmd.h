@@ -244,6 +244,32 @@ int wmd_conv_bf16_fwd(const wmd_conv_args* args, int terms, void* stream);
 int wmd_conv_bf16_num_configs(void);
 const char* wmd_conv_bf16_config_name(int i);
 
+/* ------------------------------------------------------------------ *
+ * Winograd F(4x4,3x3) in three passes, for 3x3 layers with few pixels and many channels (the coarse up+skip layers of the
+ * trunk): input transform V = B^T d B, 36 batched GEMMs M_p = U_p^T V_p on v_mfma_f32_32x32x2_f32, output transform
+ * y = act(A^T M A + bias) -- "wino44_input_kernel", "wino44_gemm_kernel", "wino44_output_kernel" in the profiler.  36 matrix-
+ * pipe positions per 16 outputs (the fused F(2x2,3x3) kernels execute 64); V and M live in the caller's workspace.  Same
+ * operator and the same wmd_conv_args as wmd_conv_fwd: nearest x2 upsample of x1 (read at its own resolution: 25 of the 36
+ * positions carry its channels), concat with x2, border addressing, bias, activation.  Points 0, +-1, +-2, inf: the rounding
+ * error is ~2e-5 of the tensor's scale at 512 input channels (the fused F(2x2,3x3) kernels: 4e-7), which is why wmd_conv_fwd never chooses these
+ * kernels by itself: a caller opts in per layer (ops.conv3x3_wino44_nograd, inference only).
+ * Supported (everything else WMD_ERR_UNSUPPORTED before any launch; wmd_conv_wino44_supported answers without a HIP call):
+ *   ksize = 3; up1 1 or 2; pad ZERO, REFLECT or REPLICATE; any C1, C2, Cout up to 65536; gate, in_mask, out_mask, out_tiles
+ *   NULL; tune_cfg = tune_ksplit = 0 (one configuration; the reduction is never split: x1's channels, then x2's, in one
+ *   workgroup -- a launch repeats bit for bit); every tensor and image below 2 GiB.
+ * wp = the image of wmd_conv_pack_weights_wino44 for the same (Cout, C1, C2, up1): U = G g G^T computed in double and
+ *   rounded once, [36][(C1p + C2p) / 4][Coutp][4] floats (channel counts rounded up to 32 each, Cout to 32); for up1 = 2 the rows of
+ *   x1's channels are 0 at the 11 positions the upsampled operand does not reach (a replicated line transforms to 0 there).
+ * Workspace: wmd_conv_wino44_workspace_floats(args) floats = V [36][(C1p + C2p) / 4][NTp][4] + M [36][Coutp][NTp] (NTp = the number of
+ *   4x4 output tiles B ceil(H/4) ceil(W/4), rounded up to 32); smaller or NULL: WMD_ERR_WORKSPACE.  No host synchronisation:
+ *   the three launches can be captured.
+ * ------------------------------------------------------------------ */
+size_t wmd_conv_packed_weight_floats_wino44(int Cout, int C1, int C2);
+int wmd_conv_pack_weights_wino44(const float* w, float* wp, int Cout, int C1, int C2, int up1, void* stream);
+int wmd_conv_wino44_supported(const wmd_conv_args* args);
+size_t wmd_conv_wino44_workspace_floats(const wmd_conv_args* args);
+int wmd_conv_wino44_fwd(const wmd_conv_args* args, void* stream);
+
 /* dz = dy * act'(y)  (y = the activation OUTPUT saved by the forward). In place allowed. */
 int wmd_act_bwd(const float* dy, const float* y, float* dz, size_t n, int act, float slope, void* stream);
 

@@ -179,6 +179,11 @@ SIGNATURES = {
     "wmd_conv_bf16_supported": (C.c_int, [C.POINTER(ConvArgs), C.c_int]),
     "wmd_conv_bf16_workspace_floats": (C.c_size_t, [C.POINTER(ConvArgs), C.c_int]),
     "wmd_conv_bf16_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.c_void_p]),
+    "wmd_conv_packed_weight_floats_wino44": (C.c_size_t, [C.c_int] * 3),
+    "wmd_conv_pack_weights_wino44": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "wmd_conv_wino44_supported": (C.c_int, [C.POINTER(ConvArgs)]),
+    "wmd_conv_wino44_workspace_floats": (C.c_size_t, [C.POINTER(ConvArgs)]),
+    "wmd_conv_wino44_fwd": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
     "wmd_conv_bf16_num_configs": (C.c_int, []),
     "wmd_conv_bf16_config_name": (C.c_char_p, [C.c_int]),
     "wmd_act_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_size_t, C.c_int, C.c_float, C.c_void_p]),

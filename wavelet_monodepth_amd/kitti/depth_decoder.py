@@ -59,6 +59,9 @@ class DepthWaveProgressiveDecoder(nn.Module):
         self.sigmoid = nn.Sigmoid()
         self.tanh = nn.Tanh()
         self._graph_mode = False
+        # graph mode (enable_graph / bind_inputs: the deployed, fixed-shape inference form) also takes the remembered trunk routes
+        # (ops.conv3x3_routed_nograd); eager() keeps them, so a profiling pass runs what the replays run
+        self._use_routes = False
         self._edge = None         # layers.DeferredActivation of the current call's last feature (encoder edge), if any
         self._graphs = GraphCache()
         self.stack_heads = os.environ.get("WMD_STACKED_HEADS", "1") == "1"   # training: one launch per stage over all heads of a level
@@ -220,7 +223,7 @@ class DepthWaveProgressiveDecoder(nn.Module):
                 dst.copy_(src)
         self._ptr_max, self._ptr_seen, self._ptr_keys = int(pointer_sets), {}, set()
         self.static_route = {"buffers": 0, "pointer_replay": 0, "copy": 0}    # forwards by route (diagnostics; bench.py reports it)
-        self._graph_mode = True
+        self._graph_mode = self._use_routes = True
         self._graphs.shared_pool = torch.cuda.graph_pool_handle()   # the pointer-set captures share one memory pool
         with torch.no_grad():
             self.forward(self.static_inputs)          # warm-up + capture now, not inside the first timed call
@@ -280,7 +283,7 @@ class DepthWaveProgressiveDecoder(nn.Module):
                 self.outputs = self._forward_two_streams(input_features)
             else:
                 self.outputs = self._graphs.run(self._forward_impl, input_features, self.parameters(),
-                                                extra_key=(("edge",) + edge.key() if edge is not None else ()) + (self.trunk_precision,),
+                                                extra_key=(("edge",) + edge.key() if edge is not None else ()) + (self.trunk_precision, ops.tuner.generation),
                                                 retain_inputs=retain)
             return self.outputs
         return self._forward_impl(input_features)
@@ -295,7 +298,7 @@ class DepthWaveProgressiveDecoder(nn.Module):
     # stream share a memory pool (they replay in capture order); the two streams use different pools, so a buffer freed
     # during one capture can never be handed to a segment that runs concurrently; tensors that cross streams stay alive.
     def _forward_two_streams(self, input_features):
-        key = tuple((t.data_ptr(), tuple(t.shape)) for t in input_features) + tuple((p.data_ptr(), p._version) for p in self.parameters()) + (ops.pack_generation(), self.trunk_precision)
+        key = tuple((t.data_ptr(), tuple(t.shape)) for t in input_features) + tuple((p.data_ptr(), p._version) for p in self.parameters()) + (ops.pack_generation(), self.trunk_precision, ops.tuner.generation)
         ent = self._segments.get(key)
         if ent is None:
             if len(self._segments) >= 4:
@@ -332,9 +335,9 @@ class DepthWaveProgressiveDecoder(nn.Module):
         for i in range(4, 0, -1):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool_main):
-                x = self.convs[("upconv", i, 0)](x, precision=self._trunk_plan[("upconv", i, 0)])
+                x = self.convs[("upconv", i, 0)](x, precision=self._trunk_plan[("upconv", i, 0)], routed=self._use_routes)
                 skip = feats[i - 1] if self.use_skips else None
-                x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, precision=self._trunk_plan[("upconv", i, 1)])
+                x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, precision=self._trunk_plan[("upconv", i, 1)], routed=self._use_routes)
             trunk[i] = g
             keep.append(x)
             g = torch.cuda.CUDAGraph()
@@ -348,7 +351,7 @@ class DepthWaveProgressiveDecoder(nn.Module):
     def enable_graph(self, on=True):
         """Inference only: capture the whole forward (≈25 kernel launches) into hipGraph(s) per input
         signature and replay it.  Outputs then live in static buffers that the next call overwrites."""
-        self._graph_mode = bool(on)
+        self._graph_mode = self._use_routes = bool(on)
         self._graphs.clear()
         self._segments.clear()
         if not on:
@@ -391,10 +394,11 @@ class DepthWaveProgressiveDecoder(nn.Module):
             if i == 4 and edge is not None:
                 x = self.convs[("upconv", 4, 0)](x, x1_pre=edge.pre(), precision=prec[("upconv", 4, 0)])      # ReLU (+ affine) of the encoder's last block on load
             else:
-                x = self.convs[("upconv", i, 0)](x, x1_gate=elu if i < 4 else None, grad_is_dz=elu is not None, precision=prec[("upconv", i, 0)])
+                x = self.convs[("upconv", i, 0)](x, x1_gate=elu if i < 4 else None, grad_is_dz=elu is not None, precision=prec[("upconv", i, 0)],
+                                                 routed=self._use_routes)
             skip = input_features[i - 1] if (self.use_skips and i > 0) else None
             x = self.convs[("upconv", i, 1)](x, skip=skip, up=2, x1_gate=elu, grad_is_dz=elu is not None,
-                                             precision=prec[("upconv", i, 1)])  # fused upsample + concat
+                                             precision=prec[("upconv", i, 1)], routed=self._use_routes)  # fused upsample + concat
             if chain and i >= 2:        # levels 4..2: first stage now or deferred, then one completion launch (see _dense_route)
                 level = (x, self._head_params(i, 1), self._head_params(i, -1), self._head_params(i, 0) if i == 4 else None)
                 if chain_multi:

@@ -8,6 +8,7 @@ parameter belongs to a Conv2d/Linear) keep working; the holders' own forward is 
   NYUv2 flavour: NyuConv3x3(in, out, padding=...), UpSampleBlock (NYUv2/networks/layers.py:11-32,57-67)
   pose:          transformation_from_parameters, rot_from_axisangle, get_translation_matrix (KITTI/layers.py:42-117)
 """
+import torch
 import torch.nn as nn
 
 from . import ops
@@ -87,8 +88,9 @@ class Conv3x3(nn.Module):
         self.pad_mode = "reflect" if use_refl else "zero"
         self.conv = nn.Conv2d(int(in_channels), int(out_channels), 3, stride=stride, bias=use_bias)
 
-    def forward(self, x, skip=None, up=1, act="none", slope=0.0, x1_gate=None, grad_is_dz=False, x1_pre=None, precision=None):
+    def forward(self, x, skip=None, up=1, act="none", slope=0.0, x1_gate=None, grad_is_dz=False, x1_pre=None, precision=None, routed=False):
         # precision: None / "fp32" = the fp32 operators; "bf16x3" / "bf16" = ops.conv3x3_bf16_nograd (inference, opt-in)
+        # routed: the caller takes the remembered "route|conv|..." choices (ops.conv3x3_routed_nograd; inference only)
         if x1_pre is not None:      # encoder edge (inference): x is a pre-activation, activated on load
             assert skip is None
             return ops.conv2d_pre_activated(x, x1_pre, self.conv.weight, self.conv.bias, up1=up, pad=self.pad_mode, act=act, slope=slope,
@@ -98,6 +100,8 @@ class Conv3x3(nn.Module):
                 raise ValueError("precision must be 'fp32', 'bf16x3' or 'bf16', got %r" % (precision,))
             return ops.conv3x3_bf16_nograd(x, self.conv.weight, self.conv.bias, x2=skip, up1=up, pad=self.pad_mode, act=act,
                                            slope=slope, terms=ops.PRECISION_TERMS[precision])
+        if routed and not torch.is_grad_enabled() and x1_gate is None:   # the layer may run on the three-pass F(4x4,3x3) kernels
+            return ops.conv3x3_routed_nograd(x, self.conv.weight, self.conv.bias, x2=skip, up1=up, pad=self.pad_mode, act=act, slope=slope)
         return ops.conv2d_fused(x, self.conv.weight, self.conv.bias, x2=skip, up1=up, pad=self.pad_mode, act=act,
                                 slope=slope, x1_gate=x1_gate, grad_is_dz=grad_is_dz)
 
@@ -129,9 +133,10 @@ class ConvBlock(nn.Module):
             raise NotImplementedError
         self.kernel_size = kernel_size
 
-    def forward(self, x, skip=None, up=1, x1_gate=None, grad_is_dz=False, x1_pre=None, precision=None):
+    def forward(self, x, skip=None, up=1, x1_gate=None, grad_is_dz=False, x1_pre=None, precision=None, routed=False):
         if self.kernel_size == 3:
-            return self.conv(x, skip=skip, up=up, act="elu", x1_gate=x1_gate, grad_is_dz=grad_is_dz, x1_pre=x1_pre, precision=precision)
+            return self.conv(x, skip=skip, up=up, act="elu", x1_gate=x1_gate, grad_is_dz=grad_is_dz, x1_pre=x1_pre, precision=precision,
+                             routed=routed)
         if x1_pre is not None:
             raise NotImplementedError("the encoder edge feeds a 3x3 ConvBlock")
         if precision not in (None, "fp32"):

@@ -529,6 +529,130 @@ def conv3x3_bf16_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", ac
     return y
 
 
+# ---------------------------------------------------------------------------------------------
+# Winograd F(4x4,3x3) in three passes (wmd_conv_wino44_fwd): the coarse layers of the no-grad trunk, opt-in per layer
+# ---------------------------------------------------------------------------------------------
+
+_WINO44 = os.environ.get("WMD_WINO44", "1") != "0"     # 0: conv3x3_routed_nograd never leaves today's path
+_WINO44_TUNE = os.environ.get("WMD_WINO44") == "tune"  # tune: a layer without a remembered choice is timed on both paths (default: it stays)
+WINO44_MIN_TILES = 256                 # below this the GEMM rows are mostly padding (and small shapes keep today's arithmetic)
+WINO44_MAX_WORKSPACE_FLOATS = 32 << 20   # V + M beyond 128 MB: the fine layers, where the two extra passes cost more than the MFMAs saved
+_wino44_route = {}                     # route key -> bool: a choice made from a cache entry or a timing run holds for the process
+
+
+def pack_weights_wino44(weight, C1, up1):
+    """[Cout,C1+C2,3,3] -> the F(4x4,3x3) image of wmd_conv_pack_weights_wino44 for x1 = the first C1 channels, upsampled
+    (up1 = 2) or not; memoised on the weight like pack_weights (own slot per (C1, up1))."""
+    def build():
+        l = _lib.lib()
+        cout, cin = weight.shape[:2]
+        n = l.wmd_conv_packed_weight_floats_wino44(cout, C1, cin - C1)
+        if n == 0 or tuple(weight.shape[2:]) != (3, 3):
+            raise _lib.WmdError("no F(4x4,3x3) weight image for a %s filter with C1=%d" % (tuple(weight.shape), C1))
+        wp = torch.empty(n, device=weight.device, dtype=torch.float32)
+        check(l.wmd_conv_pack_weights_wino44(ptr(_c(weight.detach())), ptr(wp), cout, C1, cin - C1, up1, current_stream()),
+              "wmd_conv_pack_weights_wino44")
+        return (wp,)
+    return _memo(weight, "_wmd_pack_w44_%d_%d" % (C1, up1), _pack_tag(weight), build)[0]
+
+
+def _wino44_args(B, H, W, C1, up1, C2, cout, ksize, pad, act, slope):
+    return _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad], act=ACT[act],
+                         slope=float(slope), x1=None, x2=None, wp=None, bias=None, y=None, workspace=None, workspace_floats=0,
+                         tune_cfg=0, tune_ksplit=0)
+
+
+def conv3x3_wino44_supported(B, H, W, C1, up1, C2, cout, pad="reflect"):
+    """Does wmd_conv_wino44_fwd take this problem?  Shapes only, no GPU call."""
+    return bool(_lib.lib().wmd_conv_wino44_supported(C.byref(_wino44_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0))))
+
+
+def wino44_offered(B, H, W, C1, up1, C2, cout, pad="reflect"):
+    """Is the F(4x4,3x3) route a candidate for this layer?  Supported, at least WINO44_MIN_TILES 4x4 tiles, and a workspace
+    of at most WINO44_MAX_WORKSPACE_FLOATS."""
+    if not _WINO44 or B * ((H + 3) // 4) * ((W + 3) // 4) < WINO44_MIN_TILES:
+        return False
+    a = _wino44_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0)
+    n = _lib.lib().wmd_conv_wino44_workspace_floats(C.byref(a))
+    return 0 < n <= WINO44_MAX_WORKSPACE_FLOATS
+
+
+def _nograd_operands(name, x1, weight, bias, x2, up1):
+    _require_gpu(x1, x2, weight, bias)
+    if torch.is_grad_enabled() and (x1.requires_grad or weight.requires_grad or (x2 is not None and x2.requires_grad)
+                                    or (bias is not None and bias.requires_grad)):
+        raise _lib.WmdError("%s is an inference operator (use conv2d_fused to train)" % name)
+    x1, x2, bias = _c(x1), _c(x2), _c(bias)
+    B, C1 = x1.shape[0], x1.shape[1]
+    H, W = x1.shape[2] * up1, x1.shape[3] * up1
+    C2 = 0 if x2 is None else x2.shape[1]
+    if weight.shape[1] != C1 + C2:
+        raise _lib.WmdError("weight expects %d input channels, got %d" % (weight.shape[1], C1 + C2))
+    if x2 is not None and (x2.shape[0] != B or x2.shape[2] != H or x2.shape[3] != W):
+        raise _lib.WmdError("skip tensor %s does not match upsampled input %s" % (tuple(x2.shape), (B, C1, H, W)))
+    return x1, x2, bias, (B, H, W, C1, up1, C2, weight.shape[0])
+
+
+def conv3x3_wino44_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none", slope=0.0):
+    """act( conv3x3( pad( cat[ nearest_up(x1, up1), x2 ] ) ) + bias ) on the three-pass F(4x4,3x3) kernels -- the contract in
+    include/wmd.h (~1e-5 of the tensor's scale at 512 channels).  Inference operator; a problem the kernels do not take
+    raises (it is never computed on another path instead)."""
+    x1, x2, bias, (B, H, W, C1, up1, C2, cout) = _nograd_operands("conv3x3_wino44_nograd", x1, weight, bias, x2, up1)
+    l = _lib.lib()
+    a = _wino44_args(B, H, W, C1, up1, C2, cout, weight.shape[-1], pad, act, slope)
+    if not l.wmd_conv_wino44_supported(C.byref(a)):
+        raise _lib.WmdError("wmd_conv_wino44_fwd does not take this problem: %s" % l.wmd_last_error().decode())
+    wp = pack_weights_wino44(weight, C1, up1)
+    y = torch.empty((B, cout, H, W), device=x1.device, dtype=torch.float32)
+    a.x1, a.x2, a.wp, a.bias, a.y = ptr(x1), ptr(x2), ptr(wp), ptr(bias), ptr(y)
+    check(_launch_ws(a, l.wmd_conv_wino44_workspace_floats, l.wmd_conv_wino44_fwd, x1.device, False), "wmd_conv_wino44_fwd")
+    return y
+
+
+def conv3x3_routed_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none", slope=0.0):
+    """The no-grad trunk's 3x3 layer: conv2d_fused, or conv3x3_wino44_nograd where that was chosen for the layer's signature.
+    The choice is made once per process and signature by tuner.choose under a key of its own ("route|conv|..."; candidates
+    "fused" -- first: what a stream capture without a remembered choice and WMD_AUTOTUNE=0 get -- and "wino44"), never by the
+    generic "conv|..." key: the F(4x4,3x3) rounding is outside the generic operator tolerance.  By default only a REMEMBERED
+    choice (tuner.preload / WMD_TUNE_CACHE) routes a layer: the outputs of a decoder must not depend on what a timing run
+    found on the day.  A layer without an entry runs fused and is looked up again next time (an absent entry is no choice:
+    the answer does not depend on whether the cache was preloaded before or after the first forward); a choice read from an
+    entry holds for the process.  WMD_WINO44=tune times a layer without an entry on both paths; WMD_WINO44=0: always fused.
+    Callers: layers.Conv3x3 with routed=True -- the dense KITTI decoder in graph mode (kitti/depth_decoder.py)."""
+    def fused():
+        return conv2d_fused(x1, weight, bias, x2=x2, up1=up1, pad=pad, act=act, slope=slope)
+
+    if not _WINO44 or weight.shape[-1] != 3 or x1.dim() != 4:
+        return fused()
+    B, C1 = x1.shape[0], x1.shape[1]
+    H, W = x1.shape[2] * up1, x1.shape[3] * up1
+    C2 = 0 if x2 is None else x2.shape[1]
+    cout = weight.shape[0]
+    key = "route|conv|%d|%d|%d|%d|%d|%d|%d|3" % (B, H, W, C1, up1, C2, cout)
+    use = _wino44_route.get(key)
+    if use is None:
+        use = False
+        if tuner.remembered(key) is None and not _WINO44_TUNE:
+            return fused()
+        if wino44_offered(B, H, W, C1, up1, C2, cout, pad):
+            def launch(w44):
+                if w44:
+                    conv3x3_wino44_nograd(x1, weight, bias, x2=x2, up1=up1, pad=pad, act=act, slope=slope)
+                else:
+                    fused()
+                return 0
+            cands = [("fused", False), ("wino44", True)]
+            if _WINO44_TUNE:
+                use = tuner.choose(key, cands, launch)
+            else:
+                hit = tuner.remembered(key)
+                use = bool(hit is not None and dict(cands).get(hit[0], False))
+        _wino44_route[key] = use
+    if use:
+        return conv3x3_wino44_nograd(x1, weight, bias, x2=x2, up1=up1, pad=pad, act=act, slope=slope)
+    return fused()
+
+
 class _DwConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, weight, pad, up1):

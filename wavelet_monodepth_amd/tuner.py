@@ -16,6 +16,7 @@ enabled = os.environ.get("WMD_AUTOTUNE", "1") != "0"
 _cache = {}
 _cache_file = os.environ.get("WMD_TUNE_CACHE")
 _loaded = False
+generation = 0   # bumped by preload: captured graphs are keyed on it (a route that arrives later is not shadowed by an older capture)
 KSPLITS = (1, 2, 3, 4, 5, 6, 8, 12, 16)
 ranked = {}   # key -> [(config name, ksplit, ms)] of the last isolated sweep, best first (tools/step_tune.py starts from these)
 
@@ -38,11 +39,16 @@ def _save():
 
 
 def preload(path):
-    """Merge a committed cache file (read-only: nothing is written back to it)."""
-    if os.path.exists(path):
-        with open(path) as f:
-            for k, v in json.load(f).items():
-                _cache.setdefault(k, tuple(v))
+    """Merge a committed cache file (read-only: nothing is written back to it) and, if it exists, its sibling
+    `<name>.routes.json`: the "route|conv|..." choices of ops.conv3x3_routed_nograd that go with those tile choices (a file of
+    their own: every entry of the tile cache names a configuration of the library's tables, a route does not)."""
+    global generation
+    generation += 1
+    for p in (path, os.path.splitext(path)[0] + ".routes.json"):
+        if os.path.exists(p):
+            with open(p) as f:
+                for k, v in json.load(f).items():
+                    _cache.setdefault(k, tuple(v))
 
 
 def config_names():
@@ -71,6 +77,12 @@ def lookup(key):
         return (0, hit[1])
     idx = _index_of(hit[0])
     return None if idx is None else (idx, hit[1])
+
+
+def remembered(key):
+    """-> the cached (label, split) of `key` as stored, or None: no table look-up, nothing is tuned."""
+    _load()
+    return _cache.get(key)
 
 
 def _time(launch, cfg, ks, reps, e0, e1):
