@@ -711,9 +711,11 @@ def test_kitti_dense_decoder_graph_modes_repeatable_in_place(dev, two_streams):
 @pytest.mark.parametrize("C,H,W", [(32, 12, 40), (64, 9, 28), (128, 6, 20), (256, 12, 40), (32, 5, 7), (32, 10, 84),
                                    (64, 48, 160), (32, 2, 2)])
 def test_fused_head_level_vs_oracle(dev, C, H, W):
-    """wmd_head_level_fwd (C = 32, 64: one launch) and wmd_head_fused_fwd + wmd_head_shiftsum_fwd (other widths)
-    == Conv1x1 -> LeakyReLU -> Conv3x3(refl) -> sigmoid combine -> IDWT; tiles with overhang in both directions."""
-    from wavelet_monodepth_amd import ops
+    """wmd_head_level_fwd (C = 32: one launch -- head_stream_kernel, which takes every plain inference launch at this width
+    unless it is switched off, head_level_kernel then) and wmd_head_fused_fwd + wmd_head_shiftsum_fwd (C = 64, 128, 256)
+    == Conv1x1 -> LeakyReLU -> Conv3x3(refl) -> sigmoid combine -> IDWT; maps with overhang in both directions.  The launch
+    profile must name the kernels of that route."""
+    from wavelet_monodepth_amd import _lib, ops
     B, s = 2, 2
     x = t(synth.normal((B, C, H, W), "fx", 6))
     yl = t(synth.normal((B, 1, H, W), "fyl", 6)) * 2 + 4
@@ -725,8 +727,17 @@ def test_fused_head_level_vs_oracle(dev, C, H, W):
     yh_ref = (2 ** (s - 1) * sp - 2 ** (s - 1) * sn).unsqueeze(1)
     out_ref = R.haar_idwt(yl, yh_ref)
     g = lambda v: v.to(dev)
+    _lib.profile_begin()
     yh, out, disp = ops.head_fused_level_nograd(g(x), [g(v) for v in hp], [g(v) for v in hn], scale=2.0 ** (s - 1), yl=g(yl),
                                                 disp_scale=1.0 / 2 ** (s - 1), clamp01=True)
+    recs = _lib.profile_end()
+    ran = [r["kernel"] for r in recs if not r["kernel"].startswith("conv_pack")]
+    if C == 32:
+        if "WMD_HEAD_STREAM_MIN_PIXELS" not in os.environ:
+            assert ran == ["head_stream_kernel" if os.environ.get("WMD_HEAD_STREAM", "1") != "0" else "head_level_kernel"], recs
+    else:
+        first = "head_chain_kernel" if os.environ.get("WMD_HEAD_CHAIN", "1") != "0" else "conv_fwd_kernel<fused head>"
+        assert ran == [first, "head_shiftsum_kernel"], recs
     assert float((yh.cpu() - yh_ref).abs().max()) < 4e-6          # differences of sigmoids: absolute tolerance
     assert_close(out, out_ref, 2e-6, "idwt")
     assert_close(disp, torch.clamp(out_ref / 2 ** (s - 1), 0, 1), 2e-6, "disp")
@@ -761,8 +772,9 @@ def test_low_pass_chain_beside_the_fuse_form_vs_oracle(dev, B, H, W):
 
 @pytest.mark.parametrize("B,H,W", [(2, 160, 320), (3, 131, 270), (1, 322, 320), (7, 96, 160)])
 def test_streaming_head_level_vs_oracle(dev, B, H, W):
-    """Round 6: head_stream_kernel (wmd_head_stream.hip) takes wmd_head_level_fwd's plain inference launches from 100 000
-    pixels on (strip segments of 32 columns streamed through a ring of tap-partial planes; the GEMM waves' LDS traffic and
+    """Round 6: head_stream_kernel (wmd_head_stream.hip) takes wmd_head_level_fwd's plain inference launches at every size
+    (WMD_HEAD_STREAM_MIN_PIXELS defaults to 0; the small maps are in test_gpu_head_fwd.py), here at 100 000 pixels and more
+    (strip segments of 32 columns streamed through a ring of tap-partial planes; the GEMM waves' LDS traffic and
     wait counts are hand-written) -- same contract as the tile kernel: Conv1x1 -> LeakyReLU -> Conv3x3(refl) -> sigmoid combine
     -> IDWT -> clamp.  Whole strips, ragged last strips / segments (270 = 8 x 32 + 14 columns, 131 rows), one frame taller than
     wide, several units per block; every output against the oracle, and the launch must really be the streaming kernel."""

@@ -148,6 +148,7 @@ struct ConvKArgs {
     float* t;           // [B, sides*27, H*W]
     int t_ctot;
     int t_row0;   // first plane of t this launch writes
+    int t_rows;   // rows of a side's tap-partial tile that are planes of t: 27, or 9 for the low-pass chain (planes 54..62; 63..80 stay untouched)
     // optional multiplicative gate of the final output (data-gradient path): y *= gate_act'(gate), gate laid out like y
     const float* gate;
     int gate_act;

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_fwd_kernel(const ConvKArgs a
 #pragma unroll
         for (int j = 0; j < R2W; ++j) {
             const int r2 = (WM == 1 ? j : wm) * 16 + (lane & 15);
-            if (r2 >= 27) continue;
+            if (r2 >= a.t_rows) continue;
             float* tb = a.t + ((size_t)b * a.t_ctot + a.t_row0 + by * 27 + r2) * plane2;
 #pragma unroll
             for (int n = 0; n < NR; ++n) {
@@ -1108,6 +1108,7 @@ int head_fuse_launch(const float* x, const float* wp1, const float* bias1, const
     a.t = t;
     a.t_ctot = t_planes;
     a.t_row0 = low_pass ? 54 : 0;
+    a.t_rows = low_pass ? 9 : 27;
     const double pix = (double)B * plane;
     if (low_pass) {
         // 64 mid channels = one 16-row tile per wave of a 4-wave block; the second GEMM (K = 64) gives rows 0..8

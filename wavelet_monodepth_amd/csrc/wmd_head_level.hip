@@ -286,6 +286,17 @@ __global__ __launch_bounds__(NW * 64, 2) void head_level_kernel(const wmd_head_l
     // ---- 4. nine-tap shift-sum ----------------------------------------------------------------------------------------
     if (tid < HL_NPIX) {
     const int q_shift = (tid / HL_TW) * PW + tid % HL_TW;   // patch position of this thread's pixel, tap (0,0)
+    // zero padding pads mid, not x: a halo position beyond the border holds LeakyReLU(b1) (GEMM 1 of a zero column), which the
+    // padded 3x3 of the reference never reads -- those taps are left out (reflect / replicate: mid at the padded coordinate, all nine)
+    unsigned tap_ok = 0x1ffu;
+    if (a.pad_mode == WMD_PAD_ZERO) {
+        tap_ok = 0;
+#pragma unroll
+        for (int tp = 0; tp < 9; ++tp) {
+            const int gy = py + tp / 3 - 1, gx = px + tp % 3 - 1;
+            tap_ok |= (gy >= 0 && gy < H && gx >= 0 && gx < W) ? 1u << tp : 0u;
+        }
+    }
     float hs[2][3];
 #pragma unroll
     for (int sd = 0; sd < 2; ++sd) {
@@ -294,7 +305,10 @@ __global__ __launch_bounds__(NW * 64, 2) void head_level_kernel(const wmd_head_l
         for (int co = 0; co < 3; ++co) {
             float s = b3v[sd][co];
 #pragma unroll
-            for (int tp = 0; tp < 9; ++tp) s += ts[(co * 9 + tp) * PS + ((q_shift + (tp / 3) * PW + tp % 3) ^ hl_swz(co * 9 + tp))];
+            for (int tp = 0; tp < 9; ++tp) {
+                const float v = ts[(co * 9 + tp) * PS + ((q_shift + (tp / 3) * PW + tp % 3) ^ hl_swz(co * 9 + tp))];
+                s += (tap_ok >> tp & 1u) ? v : 0.f;
+            }
             hs[sd][co] = s;
         }
     }
