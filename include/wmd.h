@@ -987,6 +987,51 @@ int wmd_nyu_inputs(const unsigned char* image_u8, const unsigned char* depth_u8,
                    unsigned char* image_resized, unsigned char* depth_resized, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Colour images of the predictions (csrc/wmd_viz.hip)
+ * ------------------------------------------------------------------ */
+
+/* The three places the reference turns a map into a picture, for a batch in device memory, with the bytes numpy 2.2 and
+ * matplotlib 3.10 give on the host.  Common to all three: `lut` is a device pointer to 768 bytes, 256 rows of (r, g, b) --
+ * no table is compiled into the library; everything is enqueued on `stream`; no host synchronisation, no host read and no
+ * allocation inside a call; the number of launches does not depend on B (at most 65535).  A row index is taken from a
+ * float32 t the way Colormap.__call__ does: xa = t * 256 (float32); xa < 0 -> row 0, xa >= 256 -> row 255, else trunc(xa).
+ * workspace: 4-byte aligned; it is overwritten, its contents on entry do not matter.
+ *
+ * wmd_viz_disparity (KITTI/test_simple.py:144-175).  disp [B,h,w] float32 -> rgb [B,H,W,3] uint8; optional outputs (NULL to
+ * skip): resized [B,H,W] float32, range [B,2] = (vmin, vmax) per image.  Every value of the resized map must be FINITE.
+ *   1. resized = wmd_upsample_bilinear_fwd of disp to (H, W) with align_corners = 0 -- that kernel, the same bits; written
+ *      once (to `resized`, or to the workspace) and read by every later pass.  (h, w) == (H, W): the map is used as it is.
+ *   2. vmin = min of the map.
+ *   3. vmax = np.percentile(map, percentile) of a float32 array, whose index arithmetic is float32: n = H W,
+ *        qf = (float)percentile / 100.f;  vi = (float)(n - 1) * qf;  k = floor(vi);  g = vi - k;
+ *        a = s[k], b = s[min(k + 1, n - 1)] (s = the sorted map);  d = b - a;
+ *        vmax = g < 0.5 ? a + d * g : b - d * (1 - g), every operation rounded to float32.
+ *      a comes from a three-level radix select (11 + 11 + 10 bits) over the sign-flipped bit patterns, b from the counts of
+ *      the last level; nothing is sorted.  -0 and +0 are distinct keys and equal values.
+ *   4. vmin == vmax: every pixel gets row 0.  Otherwise Normalize's in-place float32 array with float64 scalars:
+ *        t = (float)((double)x - (double)vmin);  t = (float)((double)t / ((double)vmax - (double)vmin));  row as above.
+ * Five launches (four when the size does not change).  workspace: wmd_viz_workspace_bytes(B, H, W) bytes (0 for a bad
+ * shape; monotone in each argument); a short one is WMD_ERR_WORKSPACE.  Refused before any HIP call: a NULL disp, lut, rgb
+ * or workspace, a percentile outside [0, 100] or NaN, a misaligned workspace (WMD_ERR_BAD_ARG); a size < 1
+ * (WMD_ERR_BAD_SHAPE); H W >= 2^31 or B > 65535 (WMD_ERR_UNSUPPORTED).
+ *
+ * wmd_viz_colorize (NYUv2/utils.py:63-82).  x [B,n] float32 -> out uint8 [B,3,n] (channels_first != 0, what the reference
+ * returns) or [B,n,3].  All arithmetic float32: t = ((x - vmin) / den), row as above; NaN -> (0, 0, 0), matplotlib's bad
+ * colour.  auto_range == 0: vmin and den = (float)(vmax - vmin) come from the caller (den == 0: every pixel row 0);
+ * auto_range != 0: vmin = min, den = max - min of every plane on its own (x must be finite; den == 0: row 0), which takes
+ * one more launch and a workspace of wmd_viz_workspace_bytes(B, 1, 1) bytes.  Two launches at most.
+ *
+ * wmd_viz_normalize (KITTI/utils.py:22-28).  x, y [B,n] float32 (finite): y = (x - min) / d in float32, d = (float)((double)max -
+ * (double)min), 1e5 when max == min; min and max over every x[b] on its own -- B = 1 with n = the whole tensor is the
+ * reference's form.  Two launches; workspace as for the automatic range above.                                          */
+size_t wmd_viz_workspace_bytes(int B, int H, int W);
+int wmd_viz_disparity(const float* disp, int B, int h, int w, int H, int W, double percentile, const unsigned char* lut,
+                      unsigned char* rgb, float* resized, float* range, void* workspace, size_t workspace_bytes, void* stream);
+int wmd_viz_colorize(const float* x, int B, size_t n, int auto_range, float vmin, float den, const unsigned char* lut,
+                     unsigned char* out, int channels_first, void* workspace, size_t workspace_bytes, void* stream);
+int wmd_viz_normalize(const float* x, float* y, int B, size_t n, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Pose networks: from the pose trunk's last feature map to cam_T_cam, forward and backward
  * ------------------------------------------------------------------ */
 

@@ -258,7 +258,12 @@ SIGNATURES = {
     "wmd_nyu_inputs_table_ints": (C.c_size_t, [C.c_int] * 7),
     "wmd_nyu_inputs_tables": (C.c_int, [C.c_int] * 7 + [C.c_void_p, C.c_size_t]),
     "wmd_nyu_inputs": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 8 + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 6),
-    "wmd_pose_transform_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p]),
+    "wmd_viz_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "wmd_viz_disparity": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "wmd_viz_colorize": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wmd_viz_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wmd_pose_transform_fwd":(C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p]),
     "wmd_pose_transform_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p]),
     "wmd_pose_head_fwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
     "wmd_pose_head_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
