@@ -437,8 +437,9 @@ typedef struct {
     const uint8_t* yh_mask;
     /* optional [B][2] uint32 (round 4): the order-preserving keys of the running (min, max) of every frame's `out` (the new
      * low-pass plane) are folded in with one atomic pair per wavefront -- the range the NEXT level's threshold needs
-     * (depth_decoder.py:308: yl.max() - yl.min()) without a reduction pass of its own.  key(f) = bits(f) ^ (f < 0 ?
-     * 0xFFFFFFFF : 0x80000000); armed state (0xFFFFFFFF, 0); consumed by wmd_mask_level_lists.                             */
+     * (depth_decoder.py:308: yl.max() - yl.min()) without a reduction pass of its own.  The key is csrc/wmd_internal.h's
+     * order_key(f) = bits(f) ^ (sign ? 0xFFFFFFFF : 0x80000000), read back with order_unkey; armed state (0xFFFFFFFF, 0);
+     * consumed by wmd_mask_level_lists.                                                                                  */
     uint32_t* range_keys;
     /* optional (round 5, training forward): the sigmoid outputs themselves -- sig_p, sig_n [B,3,H,W], sig_ll [B,1,H,W] (with
      * yl_out) -- whose s (1 - s) the backward of the heads multiplies by (what wmd_head3x3_fwd returns as sig_p / sig_n)      */
@@ -615,7 +616,7 @@ int wmd_mask_level_b(const float* yl, size_t n_yl, const float* yh, float thresh
  *     that has `advance` set (the last mask launch of a decoder forward), which also stamps slot[0] = seq + 1 -- so a host
  *     that counts its forwards the same way can fetch the counts of forward k from slot k % ring_slots whenever it wants
  *     them (and verify the stamp), and a forward that nobody asks pays neither a fill, nor a copy, nor a sync.
- *   * takes the LL range from `range_keys` when given: [B][2] order-preserving uint32 keys of (min, max) that the head
+ *   * takes the LL range from `range_keys` when given: [B][2] order_key uint32 keys of (min, max) that the head
  *     kernels' epilogues maintain with atomics (wmd_head_shiftsum_args.range_keys); consumed and re-armed
  *     (0xFFFFFFFF, 0) by this launch.  Else `minmax` [B,2] floats, else every block reduces yl itself.
  * scratch: wmd_mask_level_scratch_ints(B) int32, zero-initialised ONCE by the caller, private to one stream.            */
@@ -899,14 +900,11 @@ int wmd_lidar_depth_maps(const float* points, const long long* offsets, const do
 /* KITTI training inputs: MonoDataset.preprocess (KITTI/datasets/mono_dataset.py:118-145) for N decoded frames in one call,
  * bit for bit what the reference's chain gives over Pillow 12.2: flip, 8-bit Lanczos resize, ToTensor, ColorJitter.
  *
- * Tables (host only, no HIP call).  Per axis, scale = in / out, fs = max(scale, 1), support = 3 fs,
- * ksize = ceil(support) 2 + 1 -- wmd_lanczos_ksize, 0 unless 1 <= in, out <= 32768.  Per output index xx:
- * center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), in) - xmin,
- * w[x] = L((x + xmin - center + 0.5) (1 / fs)) with L(t) = sinc(t) sinc(t / 3) on -3 <= t < 3 (libm sin, double), divided by
- * their sum, k[x] = (int)(w 2^22 +- 0.5).  wmd_lanczos_table writes bounds [out][2] = (xmin, n) and coeffs [out][ksize], zero
- * beyond n; ksize must be wmd_lanczos_ksize(in, out).  wmd_color_pyramid_tables writes the tables of a whole pyramid, level
- * after level as (bounds, coeffs) of the width then of the height, wmd_color_pyramid_table_ints ints in all (0 for a shape
- * the pyramid refuses); the caller uploads them once per shape and passes the device copy as `tables`.
+ * Tables (host only, no HIP call).  wmd_lanczos_ksize(in, out) and wmd_lanczos_table(in, out, ..) are wmd_resample_ksize and
+ * wmd_resample_table (below) with WMD_FILTER_LANCZOS: the same tables, statuses and refusals under their own names.
+ * wmd_color_pyramid_tables writes the tables of a whole pyramid, level after level as (bounds, coeffs) of the width then of
+ * the height, wmd_color_pyramid_table_ints ints in all (0 for a shape the pyramid refuses); the caller uploads them once per
+ * shape and passes the device copy as `tables`.
  *
  * wmd_color_pyramid.  frames [N,H0,W0,3] uint8 (HWC).  Level s in 0 .. num_scales-1 is h x w = (height >> s) x (width >> s),
  * resized from the uint8 level s-1 (level 0 from the frame): horizontal pass, uint8 intermediate, vertical pass, each
@@ -947,13 +945,15 @@ int wmd_color_jitter(const unsigned char* images, unsigned char* out, int N, int
  * (NYUv2/train.py:281) for B decoded samples in one call and ONE launch, bit for bit what the reference's chain gives over
  * Pillow 12.2: flip, channel swap, the gamma table, crop, 8-bit bicubic resize, ToTensor, * 1000 and the clamp.
  *
- * Tables (host only, no HIP call).  wmd_resample_ksize / wmd_resample_table are wmd_lanczos_ksize / wmd_lanczos_table with a
- * filter argument: support s = 2 for WMD_FILTER_BICUBIC, f(t) = ((a + 2) |t| - (a + 3)) t^2 + 1 for |t| < 1,
- * (((|t| - 5) |t| + 8) |t| - 4) a for |t| < 2, a = -0.5; s = 3 and L(t) as above for WMD_FILTER_LANCZOS.  Everything else is
- * the rule stated there with `3` replaced by s: ksize = ceil(s fs) 2 + 1, the bounds, the normalisation and the
- * (int)(w 2^22 +- 0.5) rounding, in double.  bounds [out][2] = (xmin, n), coeffs [out][ksize], zero beyond n.  Refused: a
- * NULL pointer, a filter that is neither, a ksize that is not wmd_resample_ksize's (WMD_ERR_BAD_ARG); in or out outside
- * 1..32768 (WMD_ERR_BAD_SHAPE; wmd_resample_ksize returns 0 for both).
+ * Tables (host only, no HIP call): Pillow's Resample.c precompute_coeffs + normalize_coeffs_8bpc, in double.  Per axis,
+ * scale = in / out, fs = max(scale, 1), support = s fs with s = 2 for WMD_FILTER_BICUBIC and 3 for WMD_FILTER_LANCZOS,
+ * ksize = ceil(support) 2 + 1 -- wmd_resample_ksize, 0 unless the filter is one of the two and 1 <= in, out <= 32768.  Per
+ * output index xx: center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0),
+ * n = min((int)(center + support + 0.5), in) - xmin, w[x] = f((x + xmin - center + 0.5) (1 / fs)) divided by their sum,
+ * k[x] = (int)(w 2^22 +- 0.5), with f(t) = ((a + 2) |t| - (a + 3)) t^2 + 1 for |t| < 1, (((|t| - 5) |t| + 8) |t| - 4) a for
+ * |t| < 2, a = -0.5 (bicubic) or f(t) = sinc(t) sinc(t / 3) on -3 <= t < 3 (Lanczos; libm sin).  wmd_resample_table writes
+ * bounds [out][2] = (xmin, n) and coeffs [out][ksize], zero beyond n.  Refused: a NULL pointer, a filter that is neither, a
+ * ksize that is not wmd_resample_ksize's (WMD_ERR_BAD_ARG); in or out outside 1..32768 (WMD_ERR_BAD_SHAPE).
  * wmd_nyu_inputs_tables writes the four bicubic tables of one call into `tables`, as (bounds, coeffs) of: image width
  * (W0 - 2 crop -> iw), image height (H0 - 2 crop -> ih), depth width (-> dw), depth height (-> dh);
  * wmd_nyu_inputs_table_ints ints in all (0 for a shape the call refuses).  The caller uploads them once per shape and passes

@@ -2,78 +2,30 @@
 oracle of wavelet_monodepth_amd.kitti_inputs.  Integer and float32 arithmetic only, written so that it equals Pillow bit
 for bit -- tests/golden/make_golden_inputs.py asserts that where Pillow is installed.
 
-    lanczos_table(n_in, n_out)          Resample.c precompute_coeffs + normalize_coeffs_8bpc -> (bounds [out,2], k [out,ksize])
-    resize(img, h, w)                   horizontal pass, uint8 intermediate, vertical pass; img uint8 [H,W,3]
+    lanczos_table(n_in, n_out), resize(img, h, w)   pillow_resample_ref's table and resize with the Lanczos filter
     pyramid(img, height, width, n, flip) -> list of uint8 levels, each resized from the previous one
     brightness / contrast / saturation / hue, jitter(img, order, factors, hue_shift)   uint8 -> uint8
     rgb_to_hsv, hsv_to_rgb              Convert.c rgb2hsv_row / hsv2rgb
     to_tensor(img)                      float32 CHW, u8 / 255 as a float32 division
 """
-import math
-
 import numpy as np
 
-PRECISION_BITS = 32 - 8 - 2
+import pillow_resample_ref as P
+from pillow_resample_ref import _pass   # noqa: F401
+
 F32 = np.float32
 
 
 def lanczos_ksize(n_in, n_out):
-    scale = n_in / n_out
-    return int(math.ceil(3.0 * max(scale, 1.0))) * 2 + 1
-
-
-def _lanczos(t):
-    if -3.0 <= t < 3.0:
-        if t == 0.0:
-            return 1.0
-        a, b = t * math.pi, t / 3.0 * math.pi
-        return math.sin(a) / a * (math.sin(b) / b)
-    return 0.0
+    return P.ksize(n_in, n_out, P.LANCZOS)
 
 
 def lanczos_table(n_in, n_out):
-    scale = n_in / n_out
-    fs = max(scale, 1.0)
-    support = 3.0 * fs
-    ksize = lanczos_ksize(n_in, n_out)
-    bounds = np.zeros((n_out, 2), np.int32)
-    coeffs = np.zeros((n_out, ksize), np.int32)
-    ss = 1.0 / fs
-    for xx in range(n_out):
-        center = (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        n = min(int(center + support + 0.5), n_in) - xmin
-        w = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(n)]
-        tot = 0.0
-        for v in w:
-            tot += v
-        for x in range(n):
-            v = w[x] / tot if tot != 0.0 else w[x]
-            coeffs[xx, x] = int(v * (1 << PRECISION_BITS) + 0.5) if v >= 0 else int(v * (1 << PRECISION_BITS) - 0.5)
-        bounds[xx] = (xmin, n)
-    return bounds, coeffs
-
-
-def _pass(img, bounds, coeffs):
-    """one pass along axis 1 of img [R,n_in,C] uint8 -> [R,n_out,C] uint8"""
-    n_out = bounds.shape[0]
-    out = np.empty((img.shape[0], n_out, img.shape[2]), np.uint8)
-    src = img.astype(np.int64)
-    for xx in range(n_out):
-        xmin, n = bounds[xx]
-        acc = np.tensordot(src[:, xmin:xmin + n, :], coeffs[xx, :n].astype(np.int64), axes=([1], [0])) + (1 << (PRECISION_BITS - 1))
-        assert np.abs(acc).max() < 2 ** 31
-        out[:, xx, :] = np.clip(acc >> PRECISION_BITS, 0, 255)
-    return out
+    return P.table(n_in, n_out, P.LANCZOS)
 
 
 def resize(img, h, w):
-    H, W = img.shape[:2]
-    if W != w:
-        img = _pass(img, *lanczos_table(W, w))
-    if H != h:
-        img = _pass(img.transpose(1, 0, 2), *lanczos_table(H, h)).transpose(1, 0, 2)
-    return np.ascontiguousarray(img)
+    return P.resize(img, h, w, P.LANCZOS)
 
 
 def pyramid(img, height, width, num_scales=4, flip=False):

@@ -188,7 +188,7 @@ def raw_call(case, dev, poison):
     levels = torch.full((pixels * 3,), 77, dtype=torch.uint8, device=dev)
     color, aug = torch.full((pixels * 3,), -1.0, device=dev), torch.full((pixels * 3,), -1.0, device=dev)
     flip, jit = torch.from_numpy(case["flip"]).to(dev), params(case["jitter"], dev)
-    tables = ki._tables(H0, W0, h, w, S, dev)
+    tables = ki.resample.device_tables("color_pyramid", (H0, W0, h, w, S), dev)
     _lib.check(l.wmd_color_pyramid(_lib.ptr(frames), N, H0, W0, h, w, S, _lib.ptr(flip), _lib.ptr(jit.enable), _lib.ptr(jit.order),
                                    _lib.ptr(jit.factors), _lib.ptr(jit.hue_shift), _lib.ptr(tables), _lib.ptr(levels), _lib.ptr(color),
                                    _lib.ptr(aug), _lib.ptr(ws), n_ws, _lib.current_stream()), "wmd_color_pyramid")
@@ -205,9 +205,9 @@ def test_bit_stable_on_a_poisoned_workspace(dev):
     levels = run_case(case, dev)
     assert np.array_equal(a[0], np.concatenate([l[0].ravel() for l in levels]))
     assert np.array_equal(a[2], np.concatenate([l[2].ravel() for l in levels]))
-    n_tables = len(ki._TABLES)
+    n_tables = len(ki.resample.DEVICE_TABLES)
     run_case(case, dev)
-    assert len(ki._TABLES) == n_tables                                               # the uploaded tables are memoised per shape
+    assert len(ki.resample.DEVICE_TABLES) == n_tables                          # the uploaded tables are memoised per shape
 
 
 def test_device_side_refusals(dev):

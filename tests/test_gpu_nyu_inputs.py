@@ -157,7 +157,7 @@ def raw_call(c, dev):
     B, H0, W0 = depth.shape
     (ih, iw), (dh, dw) = c["image_size"], c["depth_size"]
     a = aug_of(c, dev)
-    tables = ni._tables(H0, W0, c["crop"], ih, iw, dh, dw, dev)
+    tables = ni.resample.device_tables("nyu_inputs", (H0, W0, c["crop"], ih, iw, dh, dw), dev)
     assert tables.numel() == l.wmd_nyu_inputs_table_ints(H0, W0, c["crop"], ih, iw, dh, dw)
     out_i, out_d = torch.full((B, 3, ih, iw), -1.0, device=dev), torch.full((B, 1, dh, dw), -1.0, device=dev)
     disp = torch.full((B, 1, dh, dw), -1.0, device=dev)
@@ -177,9 +177,9 @@ def test_raw_call_writes_every_output_and_repeats_bit_for_bit(dev):
     check(a, *oracle("tiles_61x161"))
     for k in a:
         assert np.array_equal(a[k], b[k]), k
-    n_tables = len(ni._TABLES)
+    n_tables = len(ni.resample.DEVICE_TABLES)
     got = run(c, dev, disparity=True)
-    assert len(ni._TABLES) == n_tables                                               # the uploaded tables are memoised per shape
+    assert len(ni.resample.DEVICE_TABLES) == n_tables                                               # the uploaded tables are memoised per shape
     for k in a:
         assert np.array_equal(a[k], got[k]), k
 

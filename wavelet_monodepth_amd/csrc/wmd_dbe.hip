@@ -38,13 +38,6 @@ struct DbeTaps {
     int radius;
 };
 
-// floats <-> unsigned keys of the same order
-__device__ __forceinline__ unsigned dbe_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dbe_unkey(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k); }
-
 __global__ void dbe_init_kernel(unsigned* __restrict__ state, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) state[i] = (i % DBE_STATE == 0) ? 0xFFFFFFFFu : 0u;
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(256) void dbe_prep_kernel(const float* __restrict__
         const bool in = c < W;
         const float v = in ? pred[b * plane + (size_t)r * W + c] : 0.f;
         if (v != 0.f && v == v) {
-            const unsigned k = dbe_key(v);
+            const unsigned k = order_key(v);
             kmin = k < kmin ? k : kmin;
             kmax = k > kmax ? k : kmax;
         }
@@ -103,8 +96,8 @@ __global__ __launch_bounds__(256) void dbe_smooth_kernel(const float* __restrict
     const float* src = img + (size_t)b * H * W;
     double mn = 0.0, range = 1.0;
     if (normalise) {
-        mn = (double)dbe_unkey(state[(size_t)b * DBE_STATE + 0]);
-        range = (double)dbe_unkey(state[(size_t)b * DBE_STATE + 1]) - mn;
+        mn = (double)order_unkey(state[(size_t)b * DBE_STATE + 0]);
+        range = (double)order_unkey(state[(size_t)b * DBE_STATE + 1]) - mn;
     }
     for (int i = threadIdx.x; i < IH * IW; i += 256) {
         const int rr = i / IW, cc = i - rr * IW, y = y0 - R + rr, x = x0 - R + cc;

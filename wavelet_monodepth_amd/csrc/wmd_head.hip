@@ -388,9 +388,8 @@ __global__ void head_shiftsum_kernel(const wmd_head_shiftsum_args a) {
                     }
                 }
                 if ((uniform ? (threadIdx.x & 63) == 0 : live) && lo <= hi) {
-                    const unsigned ul = __float_as_uint(lo), uh = __float_as_uint(hi);
-                    atomicMin(&a.range_keys[2 * b], (ul & 0x80000000u) ? ~ul : (ul | 0x80000000u));
-                    atomicMax(&a.range_keys[2 * b + 1], (uh & 0x80000000u) ? ~uh : (uh | 0x80000000u));
+                    atomicMin(&a.range_keys[2 * b], order_key(lo));
+                    atomicMax(&a.range_keys[2 * b + 1], order_key(hi));
                 }
             }
             if (!live) continue;

@@ -5,7 +5,7 @@
 // file-wide `fp contract(off)` below: Pillow's x86 build has no fused multiply-add, and hipcc contracts a * b + c by default
 // (also through __fmul_rn / __fadd_rn, which are plain operators in HIP).
 //
-//   lanczos_table (host)    Resample.c precompute_coeffs + normalize_coeffs_8bpc in double with libm sin; depends on (in, out) only
+//   wmd_resample.h          the Lanczos tables (host; they depend on (in, out) only), the fixed-point pass and its clamped windows
 //   resize_level_kernel     one launch per level (the levels are a dependent chain).  A block owns 64 x th output pixels of one
 //                           image: horizontal pass over the tile's clipped row footprint into a uint8 LDS intermediate (the
 //                           flip is a mirrored gather here, source column W - 1 - x: the fixed-point tables are not mirror
@@ -19,88 +19,23 @@
 // Source pixels are read with byte loads: a native row is 3 W0 bytes (3726 at W0 = 1242) and starts on no dword boundary, and
 // a byte load can read neither before a row's first byte nor past the last byte of the last image.  Every index that comes
 // out of a device-side table or parameter array is clamped to the tensor it addresses.
-#include <math.h>
 #include <algorithm>
-#include <vector>
 #include "wmd_internal.h"
+#include "wmd_resample.h"
 
 #pragma clang fp contract(off)
 
 namespace wmd {
 
 constexpr int kInThreads = 256;
-constexpr int kTileW = 64;          // one wave per intermediate / output row of a tile
-constexpr int kMaxTileH = 16;
 constexpr int kMaxScales = 8;
-constexpr int kMaxDim = 32768;
-constexpr size_t kMaxLds = 48 * 1024;
-constexpr int kPrecisionBits = 32 - 8 - 2;
-
-// ---------------------------------------------------------------- host: coefficient tables
-static double lanczos_filter(double x) {
-    if (-3.0 <= x && x < 3.0) {
-        auto sinc = [](double t) {
-            if (t == 0.0) return 1.0;
-            t = t * M_PI;
-            return sin(t) / t;
-        };
-        return sinc(x) * sinc(x / 3);
-    }
-    return 0.0;
-}
-
-static int lanczos_ksize(int in, int out) {
-    if (in < 1 || out < 1 || in > kMaxDim || out > kMaxDim) return 0;
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(3.0 * fs) * 2 + 1;
-}
-
-static void lanczos_bound(int in, int out, int xx, int* xmin, int* n, double* center_out = nullptr) {
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, support = 3.0 * fs;
-    const double center = (xx + 0.5) * scale;
-    int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
-    if (lo < 0) lo = 0;
-    if (hi > in) hi = in;
-    *xmin = lo;
-    *n = hi - lo;
-    if (center_out) *center_out = center;
-}
-
-// bounds [out][2] = (xmin, n), coeffs [out][ksize] (zero beyond n)
-static void lanczos_table(int in, int out, int ksize, int* bounds, int* coeffs) {
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, ss = 1.0 / fs;
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < out; ++xx) {
-        int xmin, n;
-        double center;
-        lanczos_bound(in, out, xx, &xmin, &n, &center);
-        double ww = 0.0;
-        for (int x = 0; x < n; ++x) {
-            k[x] = lanczos_filter((x + xmin - center + 0.5) * ss);
-            ww += k[x];
-        }
-        int* c = coeffs + (size_t)xx * ksize;
-        for (int x = 0; x < ksize; ++x) {
-            if (x >= n) {
-                c[x] = 0;
-                continue;
-            }
-            const double w = ww != 0.0 ? k[x] / ww : k[x];
-            c[x] = w < 0 ? (int)(-0.5 + w * (1 << kPrecisionBits)) : (int)(0.5 + w * (1 << kPrecisionBits));
-        }
-        bounds[2 * xx] = xmin;
-        bounds[2 * xx + 1] = n;
-    }
-}
 
 // ---------------------------------------------------------------- the pyramid's plan (host)
-struct PyrLevel {
+struct PyrLevel : ResampleTables {
     int hi, wi, h, w;        // input and output size of the level
-    int ksh, ksv;            // table row lengths; the pass is skipped where in == out (Pillow skips it too)
     int th, rows;            // tile height, LDS intermediate rows
     size_t lds;              // dynamic LDS bytes
-    size_t hb, hk, vb, vk;   // offsets into the table, in ints
-    size_t pix;              // offset of the level in the packed outputs, in pixels (all images)
+    size_t pix;             // offset of the level in the packed outputs, in pixels (all images)
 };
 
 struct PyrPlan {
@@ -110,19 +45,6 @@ struct PyrPlan {
 };
 
 static size_t level_lds(int rows, int ksh, int ksv, int th) { return ((size_t)rows * kTileW * 3 + 3) / 4 * 4 + 4 * ((size_t)kTileW * ksh + (size_t)th * ksv); }
-
-// rows of the input that `th` output rows starting at any tile boundary read, at most
-static int level_rows(int hi, int h, int th) {
-    if (hi == h) return th;
-    int worst = 0;
-    for (int y0 = 0; y0 < h; y0 += th) {
-        int lo, n0, hi_min, n1;
-        lanczos_bound(hi, h, y0, &lo, &n0);
-        lanczos_bound(hi, h, std::min(y0 + th, h) - 1, &hi_min, &n1);
-        worst = std::max(worst, hi_min + n1 - lo);
-    }
-    return worst;
-}
 
 // 0 = ok; otherwise a status, with the message in `why`
 static int pyr_plan(int N, int H0, int W0, int height, int width, int S, PyrPlan& p, char* why, size_t why_len) {
@@ -147,23 +69,16 @@ static int pyr_plan(int N, int H0, int W0, int height, int width, int S, PyrPlan
         l.wi = wi;
         l.h = height >> s;
         l.w = width >> s;
-        l.ksh = lanczos_ksize(wi, l.w);
-        l.ksv = lanczos_ksize(hi, l.h);
-        l.hb = p.table_ints;
-        l.hk = l.hb + 2 * (size_t)l.w;
-        l.vb = l.hk + (size_t)l.w * l.ksh;
-        l.vk = l.vb + 2 * (size_t)l.h;
-        p.table_ints = l.vk + (size_t)l.h * l.ksv;
+        l.place(WMD_FILTER_LANCZOS, wi, l.w, hi, l.h, p.table_ints);
         l.pix = p.pixels;
         p.pixels += (size_t)N * l.h * l.w;
-        for (l.th = kMaxTileH;; l.th /= 2) {
-            l.rows = level_rows(hi, l.h, l.th);
-            l.lds = level_lds(l.rows, l.ksh, l.ksv, l.th);
-            if (l.lds <= kMaxLds) break;
-            if (l.th == 1) {
-                snprintf(why, why_len, "level %d (%dx%d -> %dx%d) needs %zu bytes of LDS for one output row", s, hi, wi, l.h, l.w, l.lds);
-                return WMD_ERR_UNSUPPORTED;
-            }
+        l.th = fit_tile_height([&](int th) {
+            l.rows = resample_span(WMD_FILTER_LANCZOS, hi, l.h, th);
+            return l.lds = level_lds(l.rows, l.ksh, l.ksv, th);
+        });
+        if (l.th == 0) {
+            snprintf(why, why_len, "level %d (%dx%d -> %dx%d) needs %zu bytes of LDS for one output row", s, hi, wi, l.h, l.w, l.lds);
+            return WMD_ERR_UNSUPPORTED;
         }
         hi = l.h;
         wi = l.w;
@@ -197,8 +112,6 @@ __device__ __forceinline__ JitterItem jitter_load(const JitterArgs& a, size_t n)
     }
     return j;
 }
-
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // ImagingBlend(deg, img, f) on one channel: float32, product and sum rounded apart, truncated
 __device__ __forceinline__ int blend1(int deg, int img, float f, bool inside) {
@@ -307,57 +220,37 @@ __global__ __launch_bounds__(kInThreads) void resize_level_kernel(ResizeArgs a) 
     const int ncols = min(kTileW, a.w - x0), nrow_out = min(a.th, a.h - y0);
     const bool hpass = a.wi != a.w, vpass = a.hi != a.h;
     // the tile's input rows [row_lo, row_lo + nrows), never more than the LDS holds and never outside the image
-    int row_lo = y0, nrows = nrow_out;
-    if (vpass) {
-        row_lo = min(max(a.vb[2 * y0], 0), a.hi);
-        const int last = y0 + nrow_out - 1;
-        const int row_hi = min(max(a.vb[2 * last] + a.vb[2 * last + 1], row_lo), a.hi);
-        nrows = row_hi - row_lo;
-    }
-    nrows = min(min(nrows, a.rows), a.hi - row_lo);
+    int row_lo, nrows;
+    tile_window(a.vb, vpass, y0, nrow_out, a.hi, a.rows, row_lo, nrows);
     // this thread's column of the horizontal pass
     int xmin = 0, xn = 0;
     if (lane < ncols) {
         if (hpass) {
-            xmin = min(max(a.hb[2 * (x0 + lane)], 0), a.wi);
-            xn = min(max(a.hb[2 * (x0 + lane) + 1], 0), min(a.ksh, a.wi - xmin));
-            for (int t = 0; t < a.ksh; ++t) hk_s[t * kTileW + lane] = a.hk[(size_t)(x0 + lane) * a.ksh + t];
+            tap_window(a.hb, x0 + lane, a.ksh, 0, a.wi, xmin, xn);
+            stage_hk(hk_s, a.hk, a.ksh, x0 + lane, lane);
         } else {
             xmin = x0 + lane;   // <= w - 1 = wi - 1
             xn = 1;
         }
     }
-    if (vpass)
-        for (int i = tid; i < nrow_out * a.ksv; i += kInThreads) vk_s[i] = a.vk[(size_t)y0 * a.ksv + i];
+    if (vpass) stage_vk(vk_s, a.vk, a.ksv, y0, nrow_out, tid, kInThreads);
     __syncthreads();
     const bool flip = a.flip != nullptr && a.flip[n] != 0;
     const unsigned char* img = a.src + n * (size_t)a.hi * a.wi * 3;
+    const int xs = 3 * (flip ? a.wi - 1 - xmin : xmin), step = flip ? -3 : 3;   // flipped: from the mirrored column backwards
     for (int rr = wave; rr < nrows; rr += kInThreads / kTileW) {
         if (lane >= ncols) continue;
-        const unsigned char* row = img + (size_t)(row_lo + rr) * a.wi * 3;
-        int r, g, b;
+        const unsigned char* row = img + (size_t)(row_lo + rr) * a.wi * 3 + xs;
+        int px[3];
         if (hpass) {
-            r = g = b = 1 << (kPrecisionBits - 1);
-            for (int t = 0; t < xn; ++t) {
-                const int x = flip ? a.wi - 1 - (xmin + t) : xmin + t;
-                const int k = hk_s[t * kTileW + lane];
-                r += k * (int)row[3 * x];
-                g += k * (int)row[3 * x + 1];
-                b += k * (int)row[3 * x + 2];
-            }
-            r = clip8(r >> kPrecisionBits);
-            g = clip8(g >> kPrecisionBits);
-            b = clip8(b >> kPrecisionBits);
+            resample_taps<3>(px, hk_s + lane, kTileW, row, step, xn);
         } else {
-            const int x = flip ? a.wi - 1 - xmin : xmin;
-            r = row[3 * x];
-            g = row[3 * x + 1];
-            b = row[3 * x + 2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) px[c] = row[c];
         }
         unsigned char* m = mid + ((size_t)rr * kTileW + lane) * 3;
-        m[0] = (unsigned char)r;
-        m[1] = (unsigned char)g;
-        m[2] = (unsigned char)b;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[c] = (unsigned char)px[c];
     }
     __syncthreads();
     const JitterItem jit = jitter_load(a.jit, n);
@@ -366,38 +259,22 @@ __global__ __launch_bounds__(kInThreads) void resize_level_kernel(ResizeArgs a) 
     for (int ry = wave; ry < nrow_out; ry += kInThreads / kTileW) {
         if (lane >= ncols) continue;
         const int y = y0 + ry;
-        int r, g, b;
+        int px[3];
         if (vpass) {
-            int ymin = min(max(a.vb[2 * y], row_lo), row_lo + nrows);
-            const int yn = min(max(a.vb[2 * y + 1], 0), min(a.ksv, row_lo + nrows - ymin));
-            ymin -= row_lo;
-            r = g = b = 1 << (kPrecisionBits - 1);
-            for (int t = 0; t < yn; ++t) {
-                const int k = vk_s[ry * a.ksv + t];
-                const unsigned char* m = mid + ((size_t)(ymin + t) * kTileW + lane) * 3;
-                r += k * (int)m[0];
-                g += k * (int)m[1];
-                b += k * (int)m[2];
-            }
-            r = clip8(r >> kPrecisionBits);
-            g = clip8(g >> kPrecisionBits);
-            b = clip8(b >> kPrecisionBits);
+            int ymin, yn;
+            tap_window(a.vb, y, a.ksv, row_lo, nrows, ymin, yn);
+            resample_taps<3>(px, vk_s + ry * a.ksv, 1, mid + ((size_t)ymin * kTileW + lane) * 3, kTileW * 3, yn);
         } else {
-            r = g = b = 0;
-            if (ry < nrows) {
-                const unsigned char* m = mid + ((size_t)ry * kTileW + lane) * 3;
-                r = m[0];
-                g = m[1];
-                b = m[2];
-            }
+            const unsigned char* m = mid + ((size_t)ry * kTileW + lane) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) px[c] = ry < nrows ? (int)m[c] : 0;
         }
         unsigned char* o = out + ((size_t)y * a.w + x0 + lane) * 3;
-        o[0] = (unsigned char)r;
-        o[1] = (unsigned char)g;
-        o[2] = (unsigned char)b;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = (unsigned char)px[c];
         if (jit.on) {
-            jitter_chain<true>(r, g, b, jit, 0);
-            grey_sum += (unsigned)grey_of(r, g, b);
+            jitter_chain<true>(px[0], px[1], px[2], jit, 0);
+            grey_sum += (unsigned)grey_of(px[0], px[1], px[2]);
         }
     }
     if (a.sums != nullptr && jit.on) block_add(grey_sum, a.sums + n);   // jit.on is uniform over the block
@@ -473,16 +350,10 @@ static unsigned finish_blocks(size_t hw) { return (unsigned)std::min<size_t>((si
 
 using namespace wmd;
 
-extern "C" int wmd_lanczos_ksize(int in, int out) { return lanczos_ksize(in, out); }
+extern "C" int wmd_lanczos_ksize(int in, int out) { return resample_ksize(WMD_FILTER_LANCZOS, in, out); }
 
 extern "C" int wmd_lanczos_table(int in, int out, int* bounds, int* coeffs, int ksize) {
-    const char* who = "wmd_lanczos_table";
-    if (!bounds || !coeffs) return fail(WMD_ERR_BAD_ARG, "%s: null table pointer", who);
-    const int need = lanczos_ksize(in, out);
-    if (need == 0) return fail(WMD_ERR_BAD_SHAPE, "%s: in=%d out=%d must be in 1..%d", who, in, out, kMaxDim);
-    if (ksize != need) return fail(WMD_ERR_BAD_ARG, "%s: ksize=%d, wmd_lanczos_ksize(%d, %d) = %d", who, ksize, in, out, need);
-    lanczos_table(in, out, ksize, bounds, coeffs);
-    return WMD_OK;
+    return resample_table_checked("wmd_lanczos_table", WMD_FILTER_LANCZOS, in, out, bounds, coeffs, ksize);
 }
 
 extern "C" size_t wmd_color_pyramid_table_ints(int H0, int W0, int height, int width, int num_scales) {
@@ -501,8 +372,7 @@ extern "C" int wmd_color_pyramid_tables(int H0, int W0, int height, int width, i
     if (table_ints != p.table_ints) return fail(WMD_ERR_BAD_ARG, "%s: table_ints=%zu, %zu needed", who, table_ints, p.table_ints);
     for (int s = 0; s < p.S; ++s) {
         const PyrLevel& l = p.l[s];
-        lanczos_table(l.wi, l.w, l.ksh, tables + l.hb, tables + l.hk);
-        lanczos_table(l.hi, l.h, l.ksv, tables + l.vb, tables + l.vk);
+        l.fill(WMD_FILTER_LANCZOS, l.wi, l.w, l.hi, l.h, tables);
     }
     return WMD_OK;
 }

@@ -78,6 +78,14 @@ __device__ __forceinline__ bool pad_coord(int& g, int n, int pad_mode) {
     return true;
 }
 
+// Order-preserving float <-> uint32 key: unsigned order of the keys is float order of the values, with -0 < +0 (and NaNs
+// beyond the infinity of their sign); the inverse is exact, order_unkey(order_key(f)) has f's bits.
+__device__ __forceinline__ unsigned order_key(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
 // The wavelet heads' front end.  Every WMD_HEAD* / WMD_SHIFTSUM* switch, read once per process (wmd_head.hip):
 struct HeadSwitches {
     bool chain;              // WMD_HEAD_CHAIN=0: the two-launch heads stay on the FUSE form of conv_fwd_kernel

@@ -43,15 +43,6 @@ static LidarWorkspace lidar_layout(size_t B, size_t H, size_t W) {
     return l;
 }
 
-__device__ __forceinline__ unsigned lidar_ordered(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float lidar_unordered(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // ((P0 x + P1 y) + P2 z) + P3 with every product and sum rounded on its own.  hipcc contracts a * b + c into a fused
 // multiply-add by default -- also through __dmul_rn / __dadd_rn, which are plain operators in HIP -- and a fused row moves
 // a rounding tie of u or v to the other pixel; the pragma keeps the seven operations apart.
@@ -96,7 +87,7 @@ __global__ __launch_bounds__(kLidarThreads) void lidar_scatter_kernel(const floa
         const double u = rint(p[0] / p[2]) - 1.0, v = rint(p[1] / p[2]) - 1.0;
         if (!(u >= 0.0 && v >= 0.0 && u < (double)W && v < (double)H)) continue;   // in float64: inf and NaN drop out here
         const int ui = (int)u, vi = (int)v;
-        const unsigned image = lidar_ordered((float)(vel_depth ? x : p[2]));
+        const unsigned image = order_key((float)(vel_depth ? x : p[2]));
         const size_t pixel = (size_t)vi * W + ui, key = (size_t)vi * (W - 1) + ui;   // sub2ind + 1: 0 .. H (W - 1)
         atomicMax(pix + (size_t)b * hw + pixel, ((unsigned long long)(idx + 1) << 32) | image);
         atomicMin(first + (size_t)b * nk + key, ((unsigned long long)idx << 32) | (unsigned long long)pixel);
@@ -116,8 +107,8 @@ __global__ __launch_bounds__(kLidarThreads) void lidar_resolve_kernel(const unsi
         const unsigned pixel = (unsigned)(i - b * hw), v = pixel / (unsigned)W, u = pixel - v * (unsigned)W;
         const size_t key = b * nk + (size_t)v * (W - 1) + u;
         const unsigned long long word = pix[i];
-        float val = word ? lidar_unordered((unsigned)word) : 0.f;
-        if (count[key] > 1u && (unsigned)first[key] == pixel) val = lidar_unordered(kmin[key]);   // kitti_utils.py:95-101
+        float val = word ? order_unkey((unsigned)word) : 0.f;
+        if (count[key] > 1u && (unsigned)first[key] == pixel) val = order_unkey(kmin[key]);   // kitti_utils.py:95-101
         depth[i] = val < 0.f ? 0.f : val;
     }
 }

@@ -4,8 +4,7 @@
 // bicubic resize, ToTensor, * 1000 and the clamp.  Integer and float32 arithmetic with every operation rounded on its own, hence
 // the file-wide `fp contract(off)` (wmd_inputs.hip says why).
 //
-//   resample_table (host)   Resample.c precompute_coeffs + normalize_coeffs_8bpc in double for the bicubic (a = -0.5, support 2)
-//                           and the Lanczos (support 3) filter; depends on (filter, in, out) only
+//   wmd_resample.h          the bicubic tables (host; they depend on (in, out) only), the fixed-point pass and its clamped windows
 //   nyu_inputs_kernel       ONE launch per call.  A block owns 64 x th output pixels of one image or of one depth map (the grid's
 //                           x axis lists the image tiles, then the depth tiles).  It stages the tile's source footprint -- the rows
 //                           of its vertical window times the columns of its horizontal window, inside the crop box -- in LDS,
@@ -20,11 +19,10 @@
 // and single bytes for the ragged head and tail: a row of 3 W0 or W0 bytes starts on any byte address.  No load touches a byte
 // outside the input tensors.  Every index that comes out of a device-side table or parameter array is clamped to the tensor
 // or LDS region it addresses.
-#include <math.h>
 #include <stdint.h>
 #include <algorithm>
-#include <vector>
 #include "wmd_internal.h"
+#include "wmd_resample.h"
 
 #pragma clang fp contract(off)
 
@@ -32,91 +30,15 @@ namespace wmd {
 namespace {
 
 constexpr int kNyuThreads = 256;
-constexpr int kNyuTileW = 64;         // one wave per intermediate / output row of a tile
-constexpr int kNyuMaxTileH = 16;
-constexpr int kNyuMaxDim = 32768;
-constexpr size_t kNyuMaxLds = 48 * 1024;
-constexpr int kNyuPrecisionBits = 32 - 8 - 2;
-constexpr int kNyuWaves = kNyuThreads / kNyuTileW;
-
-// ---------------------------------------------------------------- host: coefficient tables
-double bicubic_filter(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-double lanczos3_filter(double x) {
-    if (-3.0 <= x && x < 3.0) {
-        auto sinc = [](double t) {
-            if (t == 0.0) return 1.0;
-            t = t * M_PI;
-            return sin(t) / t;
-        };
-        return sinc(x) * sinc(x / 3);
-    }
-    return 0.0;
-}
-
-bool filter_ok(int filter) { return filter == WMD_FILTER_BICUBIC || filter == WMD_FILTER_LANCZOS; }
-double filter_support(int filter) { return filter == WMD_FILTER_BICUBIC ? 2.0 : 3.0; }
-
-int resample_ksize(int filter, int in, int out) {
-    if (!filter_ok(filter) || in < 1 || out < 1 || in > kNyuMaxDim || out > kNyuMaxDim) return 0;
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(filter_support(filter) * fs) * 2 + 1;
-}
-
-void resample_bound(int filter, int in, int out, int xx, int* xmin, int* n, double* center_out = nullptr) {
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, support = filter_support(filter) * fs;
-    const double center = (xx + 0.5) * scale;
-    int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
-    if (lo < 0) lo = 0;
-    if (hi > in) hi = in;
-    *xmin = lo;
-    *n = hi - lo;
-    if (center_out) *center_out = center;
-}
-
-// bounds [out][2] = (xmin, n), coeffs [out][ksize] (zero beyond n)
-void resample_table(int filter, int in, int out, int ksize, int* bounds, int* coeffs) {
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale, ss = 1.0 / fs;
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < out; ++xx) {
-        int xmin, n;
-        double center;
-        resample_bound(filter, in, out, xx, &xmin, &n, &center);
-        double ww = 0.0;
-        for (int x = 0; x < n; ++x) {
-            const double t = (x + xmin - center + 0.5) * ss;
-            k[x] = filter == WMD_FILTER_BICUBIC ? bicubic_filter(t) : lanczos3_filter(t);
-            ww += k[x];
-        }
-        int* c = coeffs + (size_t)xx * ksize;
-        for (int x = 0; x < ksize; ++x) {
-            if (x >= n) {
-                c[x] = 0;
-                continue;
-            }
-            const double w = ww != 0.0 ? k[x] / ww : k[x];
-            c[x] = w < 0 ? (int)(-0.5 + w * (1 << kNyuPrecisionBits)) : (int)(0.5 + w * (1 << kNyuPrecisionBits));
-        }
-        bounds[2 * xx] = xmin;
-        bounds[2 * xx + 1] = n;
-    }
-}
+constexpr int kNyuWaves = kNyuThreads / kTileW;
 
 // ---------------------------------------------------------------- the call's plan (host)
-struct NyuPlane {            // the image or the depth map: (Hs, Ws) -> (h, w), C bytes per pixel
+struct NyuPlane : ResampleTables {   // the image or the depth map: (Hs, Ws) -> (h, w), C bytes per pixel
     int C, h, w;
-    int ksh, ksv;            // table row lengths; a pass is skipped where in == out (Pillow skips it too)
     int th, rows, cols;      // tile height; source rows and source columns a tile reads, at most
     int stride;              // bytes of one staged source row in LDS, a multiple of 4
     unsigned off_mid, off_hk, off_vk, off_lut;   // byte offsets into the dynamic LDS
     size_t lds;
-    size_t hb, hk, vb, vk;   // offsets into the table, in ints
     int tiles_x, tiles_y;
 };
 
@@ -126,26 +48,13 @@ struct NyuPlan {
     size_t table_ints, lds;
 };
 
-// the longest source span that `t` outputs starting at any tile boundary read
-int worst_span(int in, int out, int t) {
-    if (in == out) return std::min(t, out);
-    int worst = 0;
-    for (int o = 0; o < out; o += t) {
-        int lo, n0, last_min, n1;
-        resample_bound(WMD_FILTER_BICUBIC, in, out, o, &lo, &n0);
-        resample_bound(WMD_FILTER_BICUBIC, in, out, std::min(o + t, out) - 1, &last_min, &n1);
-        worst = std::max(worst, last_min + n1 - lo);
-    }
-    return worst;
-}
-
 void plane_lds(NyuPlane& l) {
     l.stride = (l.cols * l.C + 3) / 4 * 4;
     size_t o = (size_t)l.rows * l.stride;
     l.off_mid = (unsigned)o;
-    o += ((size_t)l.rows * kNyuTileW * l.C + 3) / 4 * 4;
+    o += ((size_t)l.rows * kTileW * l.C + 3) / 4 * 4;
     l.off_hk = (unsigned)o;
-    o += 4 * (size_t)kNyuTileW * l.ksh;
+    o += 4 * (size_t)kTileW * l.ksh;
     l.off_vk = (unsigned)o;
     o += 4 * (size_t)l.th * l.ksv;
     l.off_lut = (unsigned)o;
@@ -164,8 +73,8 @@ int nyu_plan(int B, int H0, int W0, int crop, int ih, int iw, int dh, int dw, Ny
         snprintf(why, why_len, "crop=%d leaves nothing of %dx%d", crop, H0, W0);
         return WMD_ERR_BAD_SHAPE;
     }
-    if (H0 > kNyuMaxDim || W0 > kNyuMaxDim || ih > kNyuMaxDim || iw > kNyuMaxDim || dh > kNyuMaxDim || dw > kNyuMaxDim || B > 65535) {
-        snprintf(why, why_len, "sizes above %d (or B above 65535) are not implemented", kNyuMaxDim);
+    if (H0 > kMaxDim || W0 > kMaxDim || ih > kMaxDim || iw > kMaxDim || dh > kMaxDim || dw > kMaxDim || B > 65535) {
+        snprintf(why, why_len, "sizes above %d (or B above 65535) are not implemented", kMaxDim);
         return WMD_ERR_UNSUPPORTED;
     }
     p.Hs = H0 - 2 * crop;
@@ -177,25 +86,20 @@ int nyu_plan(int B, int H0, int W0, int crop, int ih, int iw, int dh, int dw, Ny
         l.C = k == 0 ? 3 : 1;
         l.h = k == 0 ? ih : dh;
         l.w = k == 0 ? iw : dw;
-        l.ksh = resample_ksize(WMD_FILTER_BICUBIC, p.Ws, l.w);
-        l.ksv = resample_ksize(WMD_FILTER_BICUBIC, p.Hs, l.h);
-        l.hb = p.table_ints;
-        l.hk = l.hb + 2 * (size_t)l.w;
-        l.vb = l.hk + (size_t)l.w * l.ksh;
-        l.vk = l.vb + 2 * (size_t)l.h;
-        p.table_ints = l.vk + (size_t)l.h * l.ksv;
-        l.cols = worst_span(p.Ws, l.w, kNyuTileW);
-        for (l.th = kNyuMaxTileH;; l.th /= 2) {
-            l.rows = worst_span(p.Hs, l.h, l.th);
+        l.place(WMD_FILTER_BICUBIC, p.Ws, l.w, p.Hs, l.h, p.table_ints);
+        l.cols = resample_span(WMD_FILTER_BICUBIC, p.Ws, l.w, kTileW);
+        l.th = fit_tile_height([&](int th) {
+            l.th = th;
+            l.rows = resample_span(WMD_FILTER_BICUBIC, p.Hs, l.h, th);
             plane_lds(l);
-            if (l.lds <= kNyuMaxLds) break;
-            if (l.th == 1) {
-                snprintf(why, why_len, "%s (%dx%d -> %dx%d) needs %zu bytes of LDS for one output row", k == 0 ? "image" : "depth", p.Hs, p.Ws, l.h,
-                         l.w, l.lds);
-                return WMD_ERR_UNSUPPORTED;
-            }
+            return l.lds;
+        });
+        if (l.th == 0) {
+            snprintf(why, why_len, "%s (%dx%d -> %dx%d) needs %zu bytes of LDS for one output row", k == 0 ? "image" : "depth", p.Hs, p.Ws, l.h,
+                     l.w, l.lds);
+            return WMD_ERR_UNSUPPORTED;
         }
-        l.tiles_x = (l.w + kNyuTileW - 1) / kNyuTileW;
+        l.tiles_x = (l.w + kTileW - 1) / kTileW;
         l.tiles_y = (l.h + l.th - 1) / l.th;
         if ((long long)l.tiles_x * l.tiles_y > (1ll << 30)) {
             snprintf(why, why_len, "%dx%d output: too many tiles for one launch", l.h, l.w);
@@ -223,8 +127,6 @@ struct NyuArgs {
     const unsigned char *flip, *perm, *lut;   // [B], [B], [B,256]; each may be null
 };
 
-__device__ __forceinline__ int nyu_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
 // one source byte, `j` bytes into the staged span of a row, to its place in LDS: pixel mirrored, channel permuted, value mapped
 template <int C>
 __device__ __forceinline__ void stage_byte(unsigned char* row_s, int j, int v, int ncs, bool flip, int inv_perm, const unsigned char* lut_s) {
@@ -244,42 +146,28 @@ __device__ __forceinline__ void nyu_tile(const NyuArgs& g, const PlaneArgs& a, u
     int* hk_s = (int*)(lds + a.off_hk);                          // [ksh][64]
     int* vk_s = (int*)(lds + a.off_vk);                          // [th][ksv]
     unsigned char* lut_s = lds + a.off_lut;                      // [256], image only
-    const int tid = threadIdx.x, lane = tid & (kNyuTileW - 1), wave = tid / kNyuTileW;
+    const int tid = threadIdx.x, lane = tid & (kTileW - 1), wave = tid / kTileW;
     const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    const int x0 = tx * kNyuTileW, y0 = ty * a.th;
-    const int ncols = min(kNyuTileW, a.w - x0), nrow_out = min(a.th, a.h - y0);
+    const int x0 = tx * kTileW, y0 = ty * a.th;
+    const int ncols = min(kTileW, a.w - x0), nrow_out = min(a.th, a.h - y0);
     const bool hpass = g.Ws != a.w, vpass = g.Hs != a.h;
     // the tile's source rows [row_lo, row_lo + nrows) and columns [col_lo, col_lo + ncs) inside the crop box: never more than
     // the LDS holds and never outside the box
-    int row_lo = y0, nrows = nrow_out;
-    if (vpass) {
-        row_lo = min(max(a.vb[2 * y0], 0), g.Hs);
-        const int last = y0 + nrow_out - 1;
-        nrows = min(max(a.vb[2 * last] + a.vb[2 * last + 1], row_lo), g.Hs) - row_lo;
-    }
-    nrows = min(min(nrows, a.rows), g.Hs - row_lo);
-    int col_lo = x0, ncs = ncols;
-    if (hpass) {
-        col_lo = min(max(a.hb[2 * x0], 0), g.Ws);
-        const int last = x0 + ncols - 1;
-        ncs = min(max(a.hb[2 * last] + a.hb[2 * last + 1], col_lo), g.Ws) - col_lo;
-    }
-    ncs = min(min(ncs, a.cols), g.Ws - col_lo);
+    int row_lo, nrows, col_lo, ncs;
+    tile_window(a.vb, vpass, y0, nrow_out, g.Hs, a.rows, row_lo, nrows);
+    tile_window(a.hb, hpass, x0, ncols, g.Ws, a.cols, col_lo, ncs);
     // this thread's column of the horizontal pass, relative to col_lo
     int xmin = 0, xn = 0;
     if (lane < ncols) {
         if (hpass) {
-            xmin = min(max(a.hb[2 * (x0 + lane)], col_lo), col_lo + ncs);
-            xn = min(max(a.hb[2 * (x0 + lane) + 1], 0), min(a.ksh, col_lo + ncs - xmin));
-            xmin -= col_lo;
-            for (int t = 0; t < a.ksh; ++t) hk_s[t * kNyuTileW + lane] = a.hk[(size_t)(x0 + lane) * a.ksh + t];
+            tap_window(a.hb, x0 + lane, a.ksh, col_lo, ncs, xmin, xn);
+            stage_hk(hk_s, a.hk, a.ksh, x0 + lane, lane);
         } else {
             xmin = lane;
             xn = lane < ncs ? 1 : 0;
         }
     }
-    if (vpass)
-        for (int i = tid; i < nrow_out * a.ksv; i += kNyuThreads) vk_s[i] = a.vk[(size_t)y0 * a.ksv + i];
+    if (vpass) stage_vk(vk_s, a.vk, a.ksv, y0, nrow_out, tid, kNyuThreads);
     const bool flip = g.flip != nullptr && g.flip[n] != 0;
     int inv_perm = 0x210;
     bool table = false;
@@ -327,20 +215,12 @@ __device__ __forceinline__ void nyu_tile(const NyuArgs& g, const PlaneArgs& a, u
         const unsigned char* s = src_s + (size_t)rr * a.stride + xmin * C;
         int acc[C];
         if (hpass) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = 1 << (kNyuPrecisionBits - 1);
-            for (int t = 0; t < xn; ++t) {
-                const int k = hk_s[t * kNyuTileW + lane];
-#pragma unroll
-                for (int c = 0; c < C; ++c) acc[c] += k * (int)s[t * C + c];
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = nyu_clip8(acc[c] >> kNyuPrecisionBits);
+            resample_taps<C>(acc, hk_s + lane, kTileW, s, C, xn);
         } else {
 #pragma unroll
             for (int c = 0; c < C; ++c) acc[c] = xn ? (int)s[c] : 0;
         }
-        unsigned char* m = mid + ((size_t)rr * kNyuTileW + lane) * C;
+        unsigned char* m = mid + ((size_t)rr * kTileW + lane) * C;
 #pragma unroll
         for (int c = 0; c < C; ++c) m[c] = (unsigned char)acc[c];
     }
@@ -352,21 +232,11 @@ __device__ __forceinline__ void nyu_tile(const NyuArgs& g, const PlaneArgs& a, u
         const int y = y0 + ry;
         int acc[C];
         if (vpass) {
-            int ymin = min(max(a.vb[2 * y], row_lo), row_lo + nrows);
-            const int yn = min(max(a.vb[2 * y + 1], 0), min(a.ksv, row_lo + nrows - ymin));
-            ymin -= row_lo;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = 1 << (kNyuPrecisionBits - 1);
-            for (int t = 0; t < yn; ++t) {
-                const int k = vk_s[ry * a.ksv + t];
-                const unsigned char* m = mid + ((size_t)(ymin + t) * kNyuTileW + lane) * C;
-#pragma unroll
-                for (int c = 0; c < C; ++c) acc[c] += k * (int)m[c];
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = nyu_clip8(acc[c] >> kNyuPrecisionBits);
+            int ymin, yn;
+            tap_window(a.vb, y, a.ksv, row_lo, nrows, ymin, yn);
+            resample_taps<C>(acc, vk_s + ry * a.ksv, 1, mid + ((size_t)ymin * kTileW + lane) * C, kTileW * C, yn);
         } else {
-            const unsigned char* m = mid + ((size_t)ry * kNyuTileW + lane) * C;
+            const unsigned char* m = mid + ((size_t)ry * kTileW + lane) * C;
 #pragma unroll
             for (int c = 0; c < C; ++c) acc[c] = ry < nrows ? (int)m[c] : 0;
         }
@@ -417,14 +287,7 @@ using namespace wmd;
 extern "C" int wmd_resample_ksize(int filter, int in, int out) { return resample_ksize(filter, in, out); }
 
 extern "C" int wmd_resample_table(int filter, int in, int out, int* bounds, int* coeffs, int ksize) {
-    const char* who = "wmd_resample_table";
-    if (!bounds || !coeffs) return fail(WMD_ERR_BAD_ARG, "%s: null table pointer", who);
-    if (!filter_ok(filter)) return fail(WMD_ERR_BAD_ARG, "%s: filter=%d is neither WMD_FILTER_BICUBIC nor WMD_FILTER_LANCZOS", who, filter);
-    const int need = resample_ksize(filter, in, out);
-    if (need == 0) return fail(WMD_ERR_BAD_SHAPE, "%s: in=%d out=%d must be in 1..%d", who, in, out, kNyuMaxDim);
-    if (ksize != need) return fail(WMD_ERR_BAD_ARG, "%s: ksize=%d, wmd_resample_ksize(%d, %d, %d) = %d", who, ksize, filter, in, out, need);
-    resample_table(filter, in, out, ksize, bounds, coeffs);
-    return WMD_OK;
+    return resample_table_checked("wmd_resample_table", filter, in, out, bounds, coeffs, ksize);
 }
 
 extern "C" size_t wmd_nyu_inputs_table_ints(int H0, int W0, int crop, int ih, int iw, int dh, int dw) {
@@ -441,11 +304,7 @@ extern "C" int wmd_nyu_inputs_tables(int H0, int W0, int crop, int ih, int iw, i
     const int st = nyu_plan(1, H0, W0, crop, ih, iw, dh, dw, p, why, sizeof(why));
     if (st != WMD_OK) return fail(st, "%s: %s", who, why);
     if (table_ints != p.table_ints) return fail(WMD_ERR_BAD_ARG, "%s: table_ints=%zu, %zu needed", who, table_ints, p.table_ints);
-    for (int k = 0; k < 2; ++k) {
-        const NyuPlane& l = p.p[k];
-        resample_table(WMD_FILTER_BICUBIC, p.Ws, l.w, l.ksh, tables + l.hb, tables + l.hk);
-        resample_table(WMD_FILTER_BICUBIC, p.Hs, l.h, l.ksv, tables + l.vb, tables + l.vk);
-    }
+    for (int k = 0; k < 2; ++k) p.p[k].fill(WMD_FILTER_BICUBIC, p.Ws, p.p[k].w, p.Hs, p.p[k].h, tables);
     return WMD_OK;
 }
 

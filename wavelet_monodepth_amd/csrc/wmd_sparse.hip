@@ -87,7 +87,7 @@ struct MaskLevelKArgs {
     int n_yl, h, w, n, tiles_x;
     wmd_dilate_spec s[8];
     // ---- work-list form ----
-    unsigned* range_keys;  // optional [B][2] ordered keys of (min, max), consumed and re-armed
+    unsigned* range_keys;  // optional [B][2] order_key keys of (min, max), consumed and re-armed
     int32_t* scratch;      // non-null = work-list form
     int32_t* ring;
     int ring_slots, slot_ints, counts_off, ncounts, advance, B;
@@ -98,10 +98,6 @@ struct MaskLevelKArgs {
 // accumulators.  Everything is per frame so that no address sees more than a few hundred atomics per launch: one ticket for
 // the whole launch serialised 2 160 blocks at ~14 ns each (38 us at 12 frames).
 constexpr int kMlTicket = 0, kMlSeq = 1, kMlFrame0 = 16, kMlFrameInts = 32, kMlFTicket = 0, kMlFCnt0 = 1, kMlFTile0 = 16;
-
-__device__ __forceinline__ float key_to_float(unsigned k) {   // inverse of wmd_head_shiftsum_args.range_keys' encoding
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
 
 // One spec over one tile: a pixel's window covers coarse rows cy0..cy1 (at most NC) and columns cx0..cx1; the OR over the
 // window is the OR of the rows' bit words masked to the column range -- NC LDS words per pixel, no inner loops (a wave64
@@ -148,9 +144,9 @@ __global__ __launch_bounds__(256) void mask_level_kernel(const MaskLevelKArgs a)
     const uint8_t* mask0 = FROM_MASK ? a.mask0 + (size_t)f * npix : nullptr;
     if constexpr (!FROM_MASK) {
         float lo, hi;
-        if (a.range_keys) {  // the range the previous level's head epilogue left behind (re-armed by this launch's last block)
-            lo = key_to_float(a.range_keys[2 * f]);
-            hi = key_to_float(a.range_keys[2 * f + 1]);
+        if (a.range_keys) {  // the range the previous level's head epilogue left behind as order_key keys (re-armed by this launch's last block)
+            lo = order_unkey(a.range_keys[2 * f]);
+            hi = order_unkey(a.range_keys[2 * f + 1]);
         } else if (a.mm) {   // batched decode: every block re-reducing its frame's whole LL plane was 40 us per level at 12 frames
             lo = a.mm[2 * f];
             hi = a.mm[2 * f + 1];

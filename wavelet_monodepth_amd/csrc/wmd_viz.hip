@@ -37,12 +37,6 @@ constexpr int VZ_STATE = 8 + 3 * VZ_BINS;   // uint32 per image: [0] ~min key, [
 constexpr int VZ_THREADS = 256;
 constexpr size_t VZ_CHUNK = 4 * VZ_THREADS;   // values a block takes per step of the reducing passes
 
-__device__ __forceinline__ unsigned vz_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vz_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
 struct VzFound {
     unsigned bin;     // the bin that holds the rank
     unsigned rem;     // rank inside that bin
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_select_kernel(const float* __r
     constexpr unsigned mask = LEVEL == 2 ? 1023u : 2047u;
     unsigned ext = 0xFFFFFFFFu;   // LEVEL 0: smallest key; LEVEL 2: smallest key whose upper 22 bits are above the prefix
     auto take = [&](float value) {
-        const unsigned k = vz_key(value);
+        const unsigned k = order_key(value);
         if (LEVEL == 0) {
             atomicAdd(&lh[k >> 21], 1u);
             ext = k < ext ? k : ext;
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_minmax_kernel(const float* __r
     const float* v = x + (size_t)b * plane;
     unsigned mn = 0xFFFFFFFFu, mx = 0u;
     auto take = [&](float value) {
-        const unsigned k = vz_key(value);
+        const unsigned k = order_key(value);
         mn = k < mn ? k : mn;
         mx = k > mx ? k : mx;
     };
@@ -284,7 +278,7 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_colour_kernel(const float* __r
         const unsigned ka = prefix | f2.bin;
         unsigned kb = ka;                                        // s[k+1]: the same value while its bin holds rank + 1 too
         if (rank_next != rank && f2.rem + 1 >= f2.count) kb = f2.next != 0xFFFFFFFFu ? (prefix | f2.next) : ~st[1];
-        const float lo = vz_unkey(~st[0]), hi = vz_lerp(vz_unkey(ka), vz_unkey(kb), g);
+        const float lo = order_unkey(~st[0]), hi = vz_lerp(order_unkey(ka), order_unkey(kb), g);
         nm.lo_d = (double)lo;
         nm.den_d = (double)hi - (double)lo;
         nm.flat = lo == hi;
@@ -294,7 +288,7 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_colour_kernel(const float* __r
         }
     } else if (auto_range) {
         const unsigned* st = state + (size_t)b * VZ_STATE;
-        const float lo = vz_unkey(~st[0]), hi = vz_unkey(st[2]);
+        const float lo = order_unkey(~st[0]), hi = order_unkey(st[2]);
         nm.lo = lo;
         nm.den_f = __fsub_rn(hi, lo);
         nm.flat = nm.den_f == 0.f;
@@ -348,7 +342,7 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_normalize_kernel(const float* 
                                                                   const unsigned* __restrict__ state, size_t plane) {
     const int b = blockIdx.y;
     const unsigned* st = state + (size_t)b * VZ_STATE;
-    const float mi = vz_unkey(~st[0]), ma = vz_unkey(st[2]);
+    const float mi = order_unkey(~st[0]), ma = order_unkey(st[2]);
     const float d = ma != mi ? (float)((double)ma - (double)mi) : 1e5f;
     const float* v = x + (size_t)b * plane;
     float* o = y + (size_t)b * plane;

@@ -15,10 +15,8 @@ no CPU fallback: CPU tensors raise.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, resample
 from ._lib import check, current_stream, ptr
-
-_TABLES = {}   # (H0, W0, height, width, num_scales, device) -> int32 device tensor
 
 
 def _gpu(who, **ts):
@@ -89,24 +87,7 @@ def sample_color_jitter(B, p=0.5, generator=None):
 
 def lanczos_table(n_in, n_out):
     """(bounds int32 [out,2] = (xmin, n), coeffs int32 [out,ksize]) of Pillow's 8-bit Lanczos resize, built by the library on the host"""
-    l = _lib.lib()
-    ksize = l.wmd_lanczos_ksize(int(n_in), int(n_out))
-    if ksize == 0:
-        raise _lib.WmdError("lanczos_table: in=%d out=%d out of range" % (n_in, n_out))
-    bounds, coeffs = np.zeros((n_out, 2), np.int32), np.zeros((n_out, ksize), np.int32)
-    check(l.wmd_lanczos_table(int(n_in), int(n_out), bounds.ctypes.data, coeffs.ctypes.data, ksize), "wmd_lanczos_table")
-    return bounds, coeffs
-
-
-def _tables(H0, W0, height, width, num_scales, device):
-    key = (H0, W0, height, width, num_scales, str(device))
-    if key not in _TABLES:
-        l = _lib.lib()
-        n = l.wmd_color_pyramid_table_ints(H0, W0, height, width, num_scales)
-        host = np.zeros(max(n, 1), np.int32)
-        check(l.wmd_color_pyramid_tables(H0, W0, height, width, num_scales, host.ctypes.data, n), "wmd_color_pyramid_tables")
-        _TABLES[key] = torch.from_numpy(host).to(device)
-    return _TABLES[key]
+    return resample.table("lanczos", n_in, n_out)
 
 
 def color_pyramid(frames, height, width, num_scales=4, flip=None, jitter=None):
@@ -130,7 +111,7 @@ def color_pyramid(frames, height, width, num_scales=4, flip=None, jitter=None):
     n_ws = l.wmd_color_pyramid_workspace_bytes(N, H0, W0, height, width, num_scales)
     sizes = [(height >> s, width >> s) for s in range(max(num_scales, 0))]
     pixels = sum(N * h * w for h, w in sizes) if n_ws else 0
-    tables = _tables(H0, W0, height, width, num_scales, dev) if n_ws else torch.zeros(1, dtype=torch.int32, device=dev)
+    tables = resample.device_tables("color_pyramid", (H0, W0, height, width, num_scales), dev) if n_ws else torch.zeros(1, dtype=torch.int32, device=dev)
     frames = frames.contiguous()
     ws = torch.empty(max(n_ws, 8) // 8, device=dev, dtype=torch.int64)
     levels = torch.empty(max(pixels, 1) * 3, device=dev, dtype=torch.uint8)

@@ -15,13 +15,11 @@ import itertools
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, resample
 from ._lib import check, current_stream, ptr
+from .resample import FILTER_BICUBIC, FILTER_LANCZOS, resample_table   # noqa: F401
 
 PERMS = list(itertools.permutations(range(3)))   # RandomChannelSwap.indices: index 0 is the identity
-FILTER_BICUBIC, FILTER_LANCZOS = 0, 1
-
-_TABLES = {}   # (H0, W0, crop, ih, iw, dh, dw, device) -> int32 device tensor
 
 
 def gamma_lut(gamma):
@@ -79,30 +77,8 @@ def sample_augmentation(B, generator=None, swap_p=0.1, gamma=0.8):
     return Augmentation(flip, perm, lut)
 
 
-def resample_table(filter, n_in, n_out):
-    """(bounds int32 [out,2] = (xmin, n), coeffs int32 [out,ksize]) of Pillow's 8-bit resize with FILTER_BICUBIC or FILTER_LANCZOS"""
-    l = _lib.lib()
-    ksize = l.wmd_resample_ksize(int(filter), int(n_in), int(n_out))
-    if ksize == 0:
-        raise _lib.WmdError("resample_table: filter=%d in=%d out=%d out of range" % (filter, n_in, n_out))
-    bounds, coeffs = np.zeros((n_out, 2), np.int32), np.zeros((n_out, ksize), np.int32)
-    check(l.wmd_resample_table(int(filter), int(n_in), int(n_out), bounds.ctypes.data, coeffs.ctypes.data, ksize), "wmd_resample_table")
-    return bounds, coeffs
-
-
 def bicubic_table(n_in, n_out):
     return resample_table(FILTER_BICUBIC, n_in, n_out)
-
-
-def _tables(H0, W0, crop, ih, iw, dh, dw, device):
-    key = (H0, W0, crop, ih, iw, dh, dw, str(device))
-    if key not in _TABLES:
-        l = _lib.lib()
-        n = l.wmd_nyu_inputs_table_ints(H0, W0, crop, ih, iw, dh, dw)
-        host = np.zeros(max(n, 1), np.int32)
-        check(l.wmd_nyu_inputs_tables(H0, W0, crop, ih, iw, dh, dw, host.ctypes.data, n), "wmd_nyu_inputs_tables")
-        _TABLES[key] = torch.from_numpy(host).to(device)
-    return _TABLES[key]
 
 
 def _gpu(who, **ts):
@@ -140,7 +116,7 @@ def train_transform(image_u8, depth_u8, aug=None, is_224=False, crop=16, image_s
     l = _lib.lib()
     n_tab = l.wmd_nyu_inputs_table_ints(H0, W0, crop, ih, iw, dh, dw)
     ok = n_tab > 0 and B > 0
-    tables = _tables(H0, W0, crop, ih, iw, dh, dw, dev) if ok else torch.zeros(1, dtype=torch.int32, device=dev)
+    tables = resample.device_tables("nyu_inputs", (H0, W0, crop, ih, iw, dh, dw), dev) if ok else torch.zeros(1, dtype=torch.int32, device=dev)
     shape_i, shape_d = ((B, 3, ih, iw), (B, 1, dh, dw)) if ok else ((1,), (1,))
     image_u8, depth_u8 = image_u8.contiguous(), depth_u8.contiguous()
     out = {"image": torch.empty(shape_i, device=dev, dtype=torch.float32), "depth": torch.empty(shape_d, device=dev, dtype=torch.float32)}
