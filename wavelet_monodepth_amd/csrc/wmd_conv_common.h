@@ -315,11 +315,12 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, lds_ptr_t ds
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
 }
 
-// conv_wino32_kernel (wmd_conv_wino32.hip): tile geometry, shared with the configuration table in wmd_conv_fwd.hip.
-// Block = WN tile groups (32 Winograd tiles = 128 pixels each) x 2 position halves, one 32-out-channel slab.
-template <int TH, int TW, int WN, int CK>
-struct W32Tile {
-    static constexpr int NW = WN * 2, NT = NW * 64;
+// Patch / weight staging geometry of the 32x32x2 Winograd kernels (wmd_conv_wino32_stage.h), shared with the configuration table in
+// wmd_conv_fwd.hip: a TH x TW pixel tile = 32 Winograd tiles per tile group, chunks of CK input channels, one 32-out-channel slab,
+// NT threads.
+template <int TH, int TW, int NT, int CK>
+struct W32Patch {
+    static constexpr int TILE_H = TH, TILE_W = TW;
     static constexpr int TXB = TW / 2, TYB = TH / 2, NTILES = TXB * TYB;
     // Patch row strides are whole 16-byte groups (round 4): a tile whose patch columns all lie inside the image stages a chunk
     // with 16-byte LDS-DMA pieces -- a quarter of the staging instructions (gfx950 accepts 4-byte-aligned global addresses for
@@ -331,50 +332,45 @@ struct W32Tile {
     static constexpr int PSF = PH * PWS;
     static constexpr int PHL = TH / 2 + 2, PWL = X4OK ? ((TW / 2 + 2 + 3) / 4) * 4 : TW / 2 + 2, PSL = PHL * PWL;   // low-resolution patch of the upsampled operand
     static constexpr int GF = PWS / 4, GL = PWL / 4;       // 16-byte groups per patch row (X4OK)
-    static constexpr int NPOSF = (PSF + NT - 1) / NT, NPOSL = (PSL + NT - 1) / NT;
     static constexpr int RUN = CK * 256;       // one 16-out-channel run of a chunk: (CK/4) K-steps x 16 positions x 64 floats
     static constexpr int RUN_LDS = RUN + 16;   // the two runs a 32-lane read group touches fall on disjoint bank halves
     static constexpr int A_FLOATS = 2 * RUN_LDS;
-    static constexpr int B_FLOATS = X4OK ? ((CK * PSF + 255) / 256) * 256 : ((CK * PSF + 63) / 64) * 64;   // whole LDS-DMA runs (256 dwords of 16-byte pieces / 64 dwords; tail = padding)
     static constexpr int NAV = (2 * CK * 64 + NT - 1) / NT;   // 16-byte weight pieces per thread and chunk
-    static constexpr int BUF_FLOATS = B_FLOATS + A_FLOATS;
     static constexpr int KW = CK / 2;          // 2-channel K-steps per chunk
-    static constexpr int XCH_FLOATS = WN * 2 * 32 * 64;   // the two halves of a group trade 32 partial outputs per lane
-    static constexpr int LDS_FLOATS = 2 * BUF_FLOATS > XCH_FLOATS ? 2 * BUF_FLOATS : XCH_FLOATS;
     static constexpr int TAB_FLOATS = ((PH + PWS + PHL + PWL + 3) / 4) * 4;   // folded row / column offsets of the patch
-    static_assert(TH % 2 == 0 && TW % 8 == 0, "whole 2x2 tiles; a lane's four consecutive tiles stay in one tile row");
-    static_assert(WN * 32 >= NTILES, "more tiles than MFMA rows");
-    static_assert(CK % 4 == 0, "chunks are whole 4-channel weight fragments");
-    static_assert((LDS_FLOATS + TAB_FLOATS) * 4 <= 160 * 1024, "LDS");
 };
 
-// conv_wino32q_kernel (wmd_conv_wino32q.hip, round 5): one tile group (32 Winograd tiles = 128 pixels) x four quarter-position
-// waves, one 32-out-channel slab; same patch / weight staging geometry as W32Tile<TH, TW, 1, CK> with 256 threads.
+// conv_wino32_kernel (wmd_conv_wino32.hip): block = WN tile groups (32 Winograd tiles = 128 pixels each) x 2 position halves.
+template <int TH, int TW, int WN, int CK>
+struct W32Tile : W32Patch<TH, TW, WN * 128, CK> {
+    using P = W32Patch<TH, TW, WN * 128, CK>;
+    static constexpr int NW = WN * 2, NT = NW * 64;
+    static constexpr int NPOSF = (P::PSF + NT - 1) / NT, NPOSL = (P::PSL + NT - 1) / NT;   // GENERIC staging: positions per thread
+    static constexpr int B_FLOATS = P::X4OK ? ((CK * P::PSF + 255) / 256) * 256 : ((CK * P::PSF + 63) / 64) * 64;   // whole LDS-DMA runs (256 dwords of 16-byte pieces / 64 dwords; tail = padding)
+    static constexpr int BUF_FLOATS = B_FLOATS + P::A_FLOATS;
+    static constexpr int XCH_FLOATS = WN * 2 * 32 * 64;   // the two halves of a group trade 32 partial outputs per lane
+    static constexpr int LDS_FLOATS = 2 * BUF_FLOATS > XCH_FLOATS ? 2 * BUF_FLOATS : XCH_FLOATS;
+    static_assert(TH % 2 == 0 && TW % 8 == 0, "whole 2x2 tiles; a lane's four consecutive tiles stay in one tile row");
+    static_assert(WN * 32 >= P::NTILES, "more tiles than MFMA rows");
+    static_assert(CK % 4 == 0, "chunks are whole 4-channel weight fragments");
+    static_assert((LDS_FLOATS + P::TAB_FLOATS) * 4 <= 160 * 1024, "LDS");
+};
+
+// conv_wino32q_kernel (wmd_conv_wino32q.hip, round 5): one tile group x four quarter-position waves.
 template <int TH, int TW, int CK>
-struct W32QTile {
+struct W32QTile : W32Patch<TH, TW, 256, CK> {
+    using P = W32Patch<TH, TW, 256, CK>;
     static constexpr int NW = 4, NT = 256;
-    static constexpr int TXB = TW / 2, TYB = TH / 2, NTILES = TXB * TYB;
-    static constexpr bool X4OK = TW % 16 == 0;
-    static constexpr int PH = TH + 2, PWS = X4OK ? ((TW + 2 + 3) / 4) * 4 : TW + 2;
-    static constexpr int PSF = PH * PWS;
-    static constexpr int PHL = TH / 2 + 2, PWL = X4OK ? ((TW / 2 + 2 + 3) / 4) * 4 : TW / 2 + 2, PSL = PHL * PWL;
-    static constexpr int GF = PWS / 4, GL = PWL / 4;
-    static constexpr int RUN = CK * 256;
-    static constexpr int RUN_LDS = RUN + 16;
-    static constexpr int A_FLOATS = 2 * RUN_LDS;
-    static constexpr int B_FLOATS = ((CK * PSF + 255) / 256) * 256;   // whole LDS-DMA runs of either piece size (tail = padding)
-    static constexpr int NAV = (2 * CK * 64 + NT - 1) / NT;
-    static constexpr int BUF_FLOATS = B_FLOATS + A_FLOATS;
-    static constexpr int KW = CK / 2;
+    static constexpr int B_FLOATS = ((CK * P::PSF + 255) / 256) * 256;   // whole LDS-DMA runs of either piece size (tail = padding)
+    static constexpr int BUF_FLOATS = B_FLOATS + P::A_FLOATS;
     static constexpr int XCH_FLOATS = 4 * 32 * 64;   // the four quarters trade 32 partial outputs per lane
     static constexpr int LDS_FLOATS = 2 * BUF_FLOATS > XCH_FLOATS ? 2 * BUF_FLOATS : XCH_FLOATS;
-    static constexpr int TAB_FLOATS = ((PH + PWS + PHL + PWL + 3) / 4) * 4;
     // (narrower than W32Tile's TW % 8: the quarter kernel addresses tile slots by tslot / TXB, tslot % TXB and stores the slot pair
     //  (2 pc, 2 pc + 1) as one 16-byte piece -- TXB even keeps the pair in one tile row and the piece on a 16-byte boundary)
     static_assert(TH % 2 == 0 && TW % 4 == 0, "whole 2x2 tiles; a stored pair of tile slots stays in one tile row");
-    static_assert(NTILES <= 32 && NTILES % 2 == 0, "one tile group");
-    static_assert(CK % 4 == 0 && PWS % 2 == 0 && PSF % 2 == 0, "8-byte patch reads");
-    static_assert((LDS_FLOATS + TAB_FLOATS) * 4 <= 53 * 1024, "three blocks per CU");
+    static_assert(P::NTILES <= 32 && P::NTILES % 2 == 0, "one tile group");
+    static_assert(CK % 4 == 0 && P::PWS % 2 == 0 && P::PSF % 2 == 0, "8-byte patch reads");
+    static_assert((LDS_FLOATS + P::TAB_FLOATS) * 4 <= 53 * 1024, "three blocks per CU");
 };
 template <int TH, int TW, int CK>
 void launch_wino32q(const ConvKArgs& a, dim3 grid, hipStream_t s);   // explicit instantiations: wmd_conv_wino32q_table.inc

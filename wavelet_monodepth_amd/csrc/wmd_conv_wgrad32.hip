@@ -21,15 +21,6 @@ namespace wmd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <class F, int... I>
-__device__ __forceinline__ void wg_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void wg_static_for(F&& f) {
-    wg_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // position ownership of the two halves: identical to conv_wino32_kernel (w32_owns)
 __host__ __device__ constexpr bool wg32_owns(int hf, int xi) {
     const int r = xi / 4, c = xi % 4;
@@ -112,7 +103,11 @@ __global__ __launch_bounds__(WCO* WCI * 128, (WCO * WCI >= 4 ? 2 : 1)) void conv
         apy[i] = p < T::NPATCH ? p / PW - 1 : -(1 << 20);
         apx[i] = p % PW - 1;
     }
-    auto fold = [&](int g, int n, int& ok) {   // padded coordinate -> source coordinate, branch-free
+
+    // padded coordinate -> source coordinate, branch-free: pad_fold (wmd_internal.h) restated as a lambda.  Calling the shared
+    // function instead gives the same instructions in another order in tile_src, which runs per tile inside the MFMA stream, and
+    // cost the 4-wave configurations 1 - 2.5 % (profiles/wino32_stage_refactor.md)
+    auto fold = [&](int g, int n, int& ok) {
         const int refl = g < 0 ? -g : (g >= n ? 2 * n - 2 - g : g);
         const int clam = min(max(g, 0), n - 1);
         ok &= (int)(a.pad_mode != WMD_PAD_ZERO) | (int)(g == clam);
@@ -190,7 +185,7 @@ __global__ __launch_bounds__(WCO* WCI * 128, (WCO * WCI >= 4 ? 2 : 1)) void conv
 
     if (t_begin < t_end) {
         const TileSrc ts0 = tile_src(t_begin);
-        wg_static_for<T::NPIECES>([&](auto qc) { stage_piece(ts0, lds, decltype(qc)::value, wave); });
+        static_for<T::NPIECES>([&](auto qc) { stage_piece(ts0, lds, decltype(qc)::value, wave); });
     }
     __syncthreads();
 
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(WCO* WCI * 128, (WCO * WCI >= 4 ? 2 : 1)) void conv
             constexpr int NP = UP ? (HF == 0 ? 5 : 4) : 8;
             constexpr int S = T::KS * NP;
             fetch(0);
-            wg_static_for<T::KS>([&](auto ksc) {
+            static_for<T::KS>([&](auto ksc) {
                 constexpr int ks = decltype(ksc)::value;
                 constexpr int sl = ks & 1;
                 if constexpr (ks + 1 < T::KS) fetch(ks + 1);
@@ -288,7 +283,7 @@ __global__ __launch_bounds__(WCO* WCI * 128, (WCO * WCI >= 4 ? 2 : 1)) void conv
                         vp[7] = w32_pk_hi_fl(tp[6], tp[7]);     // -(3,2), (3,3)
                     }
                 }
-                wg_static_for<NP>([&](auto pc) {
+                static_for<NP>([&](auto pc) {
                     constexpr int p = decltype(pc)::value;
                     constexpr int xi = wg32_nth(HF, UP, p);
                     if constexpr (NEXT) {
@@ -296,7 +291,7 @@ __global__ __launch_bounds__(WCO* WCI * 128, (WCO * WCI >= 4 ? 2 : 1)) void conv
                         constexpr int s = ks * NP + p;
                         constexpr int q0 = (s * NPIECES + S - 1) / S, q1 = ((s + 1) * NPIECES + S - 1) / S;
                         constexpr int qb = q0 < NPIECES ? q0 : NPIECES, qe = q1 < NPIECES ? q1 : NPIECES;
-                        wg_static_for<qe - qb>([&](auto qc) { stage_piece(tsn, nbuf, qb + decltype(qc)::value, wave_t); });
+                        static_for<qe - qb>([&](auto qc) { stage_piece(tsn, nbuf, qb + decltype(qc)::value, wave_t); });
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     acc[wg32_slot(HF, xi)] = __builtin_amdgcn_mfma_f32_32x32x2f32(dm[xi], vp[xi >> 1][xi & 1], acc[wg32_slot(HF, xi)], 0, 0, 0);

@@ -23,23 +23,11 @@
 #include <algorithm>
 #include <type_traits>
 #include <utility>
-#include "wmd_conv_common.h"
+#include "wmd_conv_wino32_stage.h"
 
 namespace wmd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// compile-time loop: f(integral_constant<int, I>) for I = 0 .. N-1, expanded by the front end (a `#pragma unroll` loop over
-// the MFMA groups with the piece test inside exceeds the optimizer's full-unroll budget, and a rolled loop would index the
-// accumulators at run time)
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // Which half owns transformed position xi = 4 r + c.  Half 0: row 0 and the left 2x2 of rows 1-2; half 1: the rest.  Of the
 // nine positions an upsampled operand reaches (rows / columns 0, 1, 3) half 0 holds five, half 1 four.
@@ -72,15 +60,8 @@ __host__ __device__ constexpr int w32_slot(int hf, int xi) {   // accumulator in
 // A^T = [[1,1,1,0],[0,1,-1,-1]]
 __host__ __device__ constexpr int w32_at(int a, int r) { return a == 0 ? (r < 3 ? 1 : 0) : (r == 0 ? 0 : (r == 1 ? 1 : -1)); }
 
-// Activation with the kind as a compile-time constant (w32_act / w32_act2, wmd_conv_common.h): the epilogue selects ONE instantiation
-// of its store loop per launch (a run-time switch per element put ~100 scalar branches into every wave's epilogue: 12 k -> 5.5 k
-// cycles on L14).
-
-// GENERIC = false: every chunk of CK channels lies inside one source tensor, no masks (every trunk layer of the decoders).
-//   The chunk's patch is staged as ONE flattened [channel][position] run: every LDS-DMA instruction moves 64 consecutive
-//   dwords of it from per-lane offsets that are fixed for the whole layer (channel x plane + gathered position), the chunk is
-//   a scalar base -- no per-piece predication, channel arithmetic or branches in the MFMA stream; the upsampled operand takes
-//   the structured low-resolution path.
+// GENERIC = false: every chunk of CK channels lies inside one source tensor, no masks (every trunk layer of the decoders): the
+//   flattened staging of W32Stage (wmd_conv_wino32_stage.h).
 // GENERIC = true: ragged channel counts, chunks that straddle the concat boundary, block-sparse masks (in_mask / out_mask of
 //   the sparse decoders): per-channel pieces with a per-piece source choice, upsampling through the >>1 gather.
 // MASKED: the instantiation carries the block-sparse mask code (always with GENERIC; the flattened staging has a dense and a
@@ -109,303 +90,75 @@ __global__ __launch_bounds__(WN * 128, 2) void conv_wino32_kernel(const ConvKArg
     const int wn = wave % WN;
     const int hf = wave / WN;
 
-    int t, by;
-    int tick;   // this block's (pixel tile, slab) item: index of its split-K ticket counter (splitk_ticket_finish)
-    int ks_n = a.ksplit, cps = a.chunks_per_split;   // LIST: chosen below from the list's length
-    if constexpr (LIST) {
-        const int n_items = list_total(a.tile_count, a.B) * a.cob;
-        if ((int)blockIdx.x >= n_items) return;
-        list_ksplit(n_items, a.nchunks, a.ksmax, a.list_slots, ks_n, cps);
-        if ((int)blockIdx.z >= ks_n) return;
-        const int item = xcd_contiguous(blockIdx.x, n_items);
-        const int ti = item / a.cob;
-        by = item - ti * a.cob;
-        t = list_entry(a.tile_list, a.tile_count, a.B, a.tiles_x * a.tiles_y, ti);
-        tick = item;
-    } else if (a.cob > 0) {   // (pixel tile, out-channel slab) items, slab fastest, one contiguous run per XCD (see conv_fwd_kernel)
-        const int item = xcd_contiguous(blockIdx.x, gridDim.x);
-        t = item / a.cob;
-        by = item - t * a.cob;
-        tick = item;
-    } else if (a.xcd_slab) {
-        // 2-D grid, one out-channel slab per XCD (round 6): workgroup L of a z-slice runs on XCD L % 8 (tools/probes/xcc_probe.hip), so
-        // slab L % nslab with nslab a multiple of 8 keeps a slab's 1/nslab of the weight image in ONE L2 instead of streaming the whole
-        // image into all eight (counters: L0 / L1 of config 2 read inputs + 8 x 8.4 MB of weights per launch, profiles/r06_notes.md)
-        const int L = (int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y;
-        by = L % (int)gridDim.y;
-        t = L / (int)gridDim.y;
-        tick = t * (int)gridDim.y + by;
-    } else {
-        t = xcd_contiguous(blockIdx.x, gridDim.x);
-        by = blockIdx.y;
-        tick = t * (int)gridDim.y + by;
-    }
-    const int tx = t % a.tiles_x;
-    t /= a.tiles_x;
-    const int ty = t % a.tiles_y;
-    const int b = t / a.tiles_y;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const W32Item it = w32_item<T, LIST>(a);
+    if (LIST && it.none) return;
+    const int by = it.by, tick = it.tick, ks_n = it.ks_n, cps = it.cps;
+    const int b = it.b, y0 = it.y0, x0 = it.x0;
     const int ks = blockIdx.z;
     const int H = a.H, W = a.W;
     WMD_STAMP_AFTER(1, y0 + x0 + H);   // kernel arguments have arrived, the item is decoded
-    // Block-sparse: a tile without active output pixels keeps its zeros.  It does not `return` here: an early exit ahead of
-    // the pipelined body costs the DENSE launches of this same instantiation 45 % (L14: 110 -> 160 us, A/B builds on one box;
-    // the epilogue's mask code costs nothing) -- the skipped block walks an empty chunk range and stores nothing instead
-    // (prologue + an epilogue over zeros: a few thousand cycles against ~50 k for a computed tile).
+    // block-sparse: a tile without active output pixels walks an empty chunk range and stores nothing (w32_tile_inactive)
     bool skip = false;
-    if (MASKED && !LIST && a.out_mask) {
-        int any = 0;
-        for (int i = tid; i < TH * TW; i += NT) {
-            const int yy = y0 + i / TW, xx = x0 + i % TW;
-            if (yy < H && xx < W) any |= a.out_mask[(size_t)b * H * W + (size_t)yy * W + xx];
-        }
-        // (a ballot per wave + flags in LDS; __syncthreads_or pulls in the device library's work-group reduction)
-        int* flags = reinterpret_cast<int*>(lds + T::LDS_FLOATS + T::TAB_FLOATS);
-        const bool wave_any = __builtin_amdgcn_ballot_w64(any != 0) != 0;
-        if (lane == 0) flags[wave] = wave_any ? 1 : 0;
-        __syncthreads();
-        int all = 0;
-#pragma unroll
-        for (int w = 0; w < T::NW; ++w) all |= flags[w];
-        skip = __builtin_amdgcn_readfirstlane(all) == 0;
-    }
-    const bool upl = !GENERIC && a.up1 == 2;   // structured low-resolution path of the upsampled operand
+    if (MASKED && !LIST && a.out_mask) skip = w32_tile_inactive<T>(a, b, y0, x0, reinterpret_cast<int*>(lds + T::LDS_FLOATS + T::TAB_FLOATS), wave);
 
     // ---- staging geometry ---------------------------------------------------------------------------------------
-    constexpr unsigned kOOB = 0x80000000u;   // >= any num_records: the descriptor's range check returns 0
-    const size_t plane1 = (size_t)a.H1 * a.W1, plane2 = (size_t)H * W;
-    const unsigned pb1 = (unsigned)(plane1 * 4), pb2 = (unsigned)(plane2 * 4);
-    // Padded coordinate g in [-1, n] -> source coordinate, branch-free (the pad mode is uniform, everything is a select): every
-    // block of a launch computes its offsets at the same moment, so this prologue is not hidden by anything, and the branchy
-    // form (pad_coord's switch per coordinate, short-circuit tests) cost 16 k cycles per block on L14 (cycle stamps)
-    auto fold = [&](int g, int n, int& ok) {
-        const int refl = g < 0 ? -g : (g >= n ? 2 * n - 2 - g : g);
-        const int clam = min(max(g, 0), n - 1);
-        ok &= (int)(a.pad_mode != WMD_PAD_ZERO) | (int)(g == clam);
-        const int r = a.pad_mode == WMD_PAD_REFLECT ? refl : clam;
-        return min(max(r, 0), n - 1);      // tile overhang beyond the pad ring: any in-range pixel (never stored)
-    };
-    // byte offset of full-resolution patch position p inside one channel plane of x2 (o2) / of x1 (o1): generic layers
+    using Stage = W32Stage<T, CK, !GENERIC, MASKED>;
+    Stage st(a, lds, wave);
+    const size_t plane2 = st.pl.plane2;
+    // generic layers: positions tid + i * NT of one channel; byte offset of full-resolution patch position p inside one channel
+    // plane of x2 (o2) / of x1 (o1)
+    constexpr int NPOSF = GENERIC ? T::NPOSF : 1;
+    unsigned ob1[NPOSF], ob2[NPOSF];
     auto full_pos = [&](int p, unsigned& o1, unsigned& o2) {
         const int py = p / PWS, px = p - py * PWS;
         const int gy0 = y0 + py - 1, gx0 = x0 + px - 1;
         int ok = (int)(p < PSF) & (int)(gy0 <= H) & (int)(gx0 <= W);
-        const int gy = fold(gy0, H, ok), gx = fold(gx0, W, ok);
+        const int gy = pad_fold(a.pad_mode, gy0, H, ok), gx = pad_fold(a.pad_mode, gx0, W, ok);
         if (MASKED && a.in_mask) ok &= (int)(a.in_mask[(size_t)b * H * W + gy * W + gx] != 0);
         o2 = ok ? (unsigned)(gy * W + gx) * 4u : kOOB;
         const int sy = a.up1 == 2 ? gy >> 1 : gy - a.shift1, sx = a.up1 == 2 ? gx >> 1 : gx - a.shift1;
         const int ok1 = ok & (int)(sy >= 0) & (int)(sx >= 0) & (int)(sy < a.H1) & (int)(sx < a.W1);
         o1 = ok1 ? (unsigned)(sy * a.W1 + sx) * 4u : kOOB;
     };
-    // pure layers: flattened [channel][position] runs of a chunk, element tid + i * NT
-    constexpr int NPF = GENERIC ? 1 : (CK * PSF + NT - 1) / NT, NPL = GENERIC ? 1 : (CK * PSL + NT - 1) / NT;
-    // 16-byte pieces (dense flattened staging, tiles whose patch columns all lie inside the source rows): groups per thread
-    constexpr bool X4 = !GENERIC && !MASKED && T::X4OK;
-    constexpr int NPF4 = (CK * PSF / 4 + NT - 1) / NT, NPL4 = (CK * PSL / 4 + NT - 1) / NT;
-    bool x4 = false;
-    // generic layers: positions tid + i * NT of one channel
-    constexpr int NPOSF = GENERIC ? T::NPOSF : 1;
-    unsigned obF[NPF], obL[NPL], ob1[NPOSF], ob2[NPOSF];
     if constexpr (!GENERIC) {
-        // The full-resolution chunks of a pure layer all have one geometry: the skip tensor's when x1 is upsampled (x1 then
-        // takes the low-resolution path), else x1's own (a skip tensor beside a non-upsampled x1 has the same H x W).  The
-        // pad / bounds logic is separable: PH + PWS (+ PHL + PWL) threads fold one patch row or column each into a byte
-        // offset (or -1: reads zero) in a corner of LDS, and every flattened element is then channel * plane + row + column:
-        // ~20 instructions per element instead of ~80.
-        // Low-resolution halo patch of the upsampled operand: position (py, px) is source pixel (y0/2 - 1 + py, x0/2 - 1 + px).
-        // The full-resolution pad ring (row -1 / row H) maps onto it as: reflect (-1 -> 1, H -> H-2) and replicate both land in
-        // the border source pixel, zero padding stays zero; rows beyond the ring (tile overhang) are never used by a stored output.
-        int* tab = reinterpret_cast<int*>(lds + T::LDS_FLOATS);
-        constexpr int PH = T::PH, PHL = T::PHL;
-        const bool up_g = a.up1 == 2;
-        const int Hs_g = up_g ? H : a.H1, Ws_g = up_g ? W : a.W1, sh_g = up_g ? 0 : a.shift1;
-        // folded byte offset of full-resolution patch row / column t (-1: reads zero), and of the low-resolution patch's
-        auto full_rc = [&](bool row, int t) {
-            const int g0 = row ? y0 + t - 1 : x0 + t - 1, n = row ? H : W, ns = row ? Hs_g : Ws_g;
-            int ok = (int)(g0 <= n);
-            const int g = fold(g0, n, ok) - sh_g;
-            ok &= (int)(g >= 0) & (int)(g < ns);
-            return ok ? (row ? g * Ws_g * 4 : g * 4) : -1;
-        };
-        auto low_rc = [&](bool row, int t) {
-            const int s0 = row ? (y0 >> 1) - 1 + t : (x0 >> 1) - 1 + t, n = row ? a.H1 : a.W1;
-            const int sc = min(max(s0, 0), n - 1);
-            const int ok = (int)(s0 <= n) & ((int)(a.pad_mode != WMD_PAD_ZERO) | (int)(sc == s0));
-            return ok ? (row ? sc * a.W1 * 4 : sc * 4) : -1;
-        };
-        // (Round 5 measured the alternative -- every element folding its own row and column, no LDS table, no barrier: 40 VALU
-        //  instructions per element instead of two table reads.  Slower: offsets phase 3.4 k -> 4.4 k cycles on L14, 2.8 k -> 6.5 k on
-        //  the 40-wide tiles; a young wave's VALU instructions get the issue slots its SIMD partner's main loop leaves over, so the
-        //  prologue's price is its VALU count.  s_setprio 1 through the prologue and / or the epilogue: no change either.
-        //  profiles/r05_stamps.txt, profiles/r05_notes.md.)
-        {
-            int t = tid;
-            if (t < PH + PWS) tab[t] = full_rc(t < PH, t < PH ? t : t - PH);
-            else if (t < PH + PWS + PHL + PWL) {
-                t -= PH + PWS;
-                tab[PH + PWS + t] = low_rc(t < PHL, t < PHL ? t : t - PHL);
-            }
-        }
-        __syncthreads();
+        st.fill_tables(it);
         WMD_STAMP_AFTER(2, 0);   // row / column tables in LDS
-        const unsigned pbs = a.up1 == 2 ? pb2 : pb1;
-        if constexpr (X4) {
-            // every used patch column x0 - 1 .. x0 + TW (minus the shift of a data-gradient launch) inside the source row: no
-            // column is folded, a row of the patch is one contiguous run of the source row (the upsampled operand's low-resolution
-            // patch likewise: (x0 >> 1) - 1 .. (x0 + TW) >> 1).  Border tiles keep the dword pieces with their per-column folds.
-            const bool up = a.up1 == 2;
-            const int Ws = up ? W : a.W1, sh = up ? 0 : a.shift1;
-            x4 = x0 - 1 - sh >= 0 && x0 + TW - sh < Ws && !a.no_x4;
-        }
-        if (X4 && x4) {
-            const bool up = a.up1 == 2;
-            const int sh = up ? 0 : a.shift1;
-            constexpr int PH_ = T::PH, GF = T::GF, GL = T::GL, PHL_ = T::PHL;
-#pragma unroll
-            for (int i = 0; i < NPF4; ++i) {
-                const unsigned e = tid + i * NT, ch = e / (PH_ * GF), rem = e - __umul24(ch, PH_ * GF);
-                const unsigned py = rem / GF, j = rem - __umul24(py, GF);
-                const int r = tab[min(py, (unsigned)PH_ - 1)];
-                const bool ok = ch < CK && r >= 0;
-                obF[i] = ok ? ch * pbs + (unsigned)r + (unsigned)(x0 - 1 - sh + 4 * (int)j) * 4u : kOOB;
-            }
-#pragma unroll
-            for (int i = 0; i < NPL4; ++i) {
-                const unsigned e = tid + i * NT, ch = e / (PHL_ * GL), rem = e - __umul24(ch, PHL_ * GL);
-                const unsigned py = rem / GL, j = rem - __umul24(py, GL);
-                const int r = tab[PH + PWS + min(py, (unsigned)PHL_ - 1)];
-                const bool ok = ch < CK && r >= 0;
-                obL[i] = ok ? ch * pb1 + (unsigned)r + (unsigned)((x0 >> 1) - 1 + 4 * (int)j) * 4u : kOOB;
-            }
-        } else {
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const unsigned e = tid + i * NT, ch = e / PSF, pos = e - __umul24(ch, PSF);
-            const unsigned py = pos / PWS, px = pos - __umul24(py, PWS);
-            const int r = tab[py], c = tab[PH + px];
-            bool ok = ch < CK && (r | c) >= 0;
-            // block-sparse input support: the full-resolution geometry is the mask's own (wino32_pure), so the folded pixel
-            // offset indexes it directly; a masked position gathers from the out-of-range offset like a zero-padded one
-            if (MASKED && a.in_mask && ok) ok = a.in_mask[(size_t)b * plane2 + ((unsigned)(r + c) >> 2)] != 0;
-            obF[i] = ok ? ch * pbs + (unsigned)(r + c) : kOOB;
-        }
-#pragma unroll
-        for (int i = 0; i < NPL; ++i) {
-            const unsigned e = tid + i * NT, ch = e / PSL, pos = e - __umul24(ch, PSL);
-            const unsigned py = pos / PWL, px = pos - __umul24(py, PWL);
-            const int r = tab[PH + PWS + py], c = tab[PH + PWS + PHL + px];
-            bool ok = ch < CK && (r | c) >= 0;
-            if (MASKED && a.in_mask && upl && ok) {   // 2x2-constant mask (wino32_pure): source pixel (sy, sx) is masked like (2sy, 2sx)
-                const unsigned sidx = (unsigned)(r + c) >> 2, sy = sidx / (unsigned)a.W1, sx = sidx - sy * (unsigned)a.W1;
-                ok = a.in_mask[(size_t)b * plane2 + (size_t)(2 * sy) * W + 2 * sx] != 0;
-            }
-            obL[i] = ok ? ch * pb1 + (unsigned)(r + c) : kOOB;
-        }
-        }   // dword pieces
+        st.gather_offsets(it);
     } else {
 #pragma unroll
         for (int i = 0; i < NPOSF; ++i) full_pos(tid + i * NT, ob1[i], ob2[i]);
     }
     WMD_STAMP_AFTER(3, 0);   // per-lane gather offsets
-    const float* x1b = a.x1 + (size_t)b * a.C1 * plane1;
-    const float* x2b = a.x2 ? a.x2 + (size_t)b * a.C2 * plane2 : a.x1;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x1b), 0, (int)(a.C1 * plane1 * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x2b), 0, (int)(a.C2 * plane2 * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.wp), 0, (int)((size_t)a.ncot * a.nci4 * 16 * 64 * 4), 0x00020000);
-    // weights: the slab's two 16-channel runs of a chunk as 16-byte pieces; piece e -> run e / (CK*64), slot e % (CK*64)
-    unsigned aoff[T::NAV];
-#pragma unroll
-    for (int v = 0; v < T::NAV; ++v) {
-        const int e = tid + v * NT;
-        const int run = e / (CK * 64), rem = e % (CK * 64);
-        const int cot = min(by * 2 + run, a.ncot - 1);
-        aoff[v] = e < 2 * CK * 64 ? (unsigned)(((size_t)cot * a.nci4 * 16 * 64 + (size_t)rem * 4) * 4) : kOOB;
-    }
+    st.sources(it);
+    const __amdgpu_buffer_rsrc_t r1 = st.r1, r2 = st.r2;   // the generic pieces' own copies
+    const unsigned pb1 = st.pl.pb1, pb2 = st.pl.pb2;
 
-#ifdef WMD_STAMPS
-    const int c_begin_dbg = LIST ? 0 : (int)blockIdx.z * a.chunks_per_split;
-#endif
-    // Chunk kinds: UP = CK channels of the upsampled x1, staged at low resolution (pure layers only); FULL = anything else.
-    auto is_up = [&](int chunk) { return upl && (chunk + 1) * CK <= a.C1; };
-    // wave-instructions per chunk and wave: pure layers move whole 64-dword runs (the tail lanes of the last one carry the
-    // out-of-range offset and write zeros into the buffer's padding), generic layers one channel's positions at a time
-    constexpr int NPB_F = GENERIC ? CK * NPOSF : NPF, NPB_L = NPL;
-    struct ChunkSrc {   // pure layers: the chunk's descriptor and scalar byte base, resolved once per chunk
-        __amdgpu_buffer_rsrc_t r;
-        unsigned base;
-    };
-    auto chunk_src = [&](int chunk) {
-        ChunkSrc cs;
-        const int ci0 = chunk * CK;
-        const bool in1 = ci0 < a.C1;
-        cs.r = in1 ? r1 : r2;
-        cs.base = in1 ? (unsigned)ci0 * pb1 : (unsigned)(ci0 - a.C1) * pb2;
-        return cs;
-    };
-    auto stage_weight_piece = [&](int chunk, float* bufp, int v) {
-#ifdef WMD_STAMPS
-        if ((a.dbg_mode & 4) && chunk > c_begin_dbg + 1) return;   // timing experiment: no weight traffic after the first two chunks (results wrong)
-#endif
-        const unsigned soffA = (unsigned)chunk * (unsigned)(T::RUN * 4);
-        const int e0 = wave * 64 + v * NT;   // first piece of this wave-instruction (a multiple of 64: inside one run)
-        if (T::NAV * NT == 2 * CK * 64 || e0 < 2 * CK * 64)   // wave-uniform: whole wave-instructions only
-            lds_dma16(rw, (lds_ptr_t)(bufp + T::B_FLOATS + (e0 / (CK * 64)) * T::RUN_LDS + (e0 % (CK * 64)) * 4), aoff[v], soffA);
-    };
+    // wave-instructions per chunk and wave of a FULL chunk's patch: generic layers stage one channel's positions at a time
+    constexpr int NPB_F = GENERIC ? CK * NPOSF : Stage::NPF, NPB_L = Stage::NPL;
     auto stage_full_piece = [&](int chunk, float* bufp, int q, const ChunkSrc& cs) {
-#ifdef WMD_STAMPS
-        if ((a.dbg_mode & 8) && q < NPB_F && chunk > c_begin_dbg + 1) return;   // timing experiment: no patch traffic either
-#endif
-        if (q < NPB_F) {
-            if constexpr (!GENERIC) {
-                if (X4 && x4) {      // block-uniform: 64 lanes x 16 bytes = 256 consecutive dwords of the chunk's run per instruction
-                    if (q < NPF4 && ((q + 1) * NT * 4 <= CK * PSF || (wave * 64 + q * NT) * 4 < CK * PSF))
-                        lds_dma16(cs.r, (lds_ptr_t)(bufp + (wave * 64 + q * NT) * 4), obF[q], cs.base);
-                } else if ((q + 1) * NT <= CK * PSF || wave * 64 + q * NT < CK * PSF)   // wave-uniform: skip wholly empty runs
-                    lds_dma4(cs.r, (lds_ptr_t)(bufp + wave * 64 + q * NT), obF[q], cs.base);
-            } else {
-                const int j = q / NPOSF, i = q % NPOSF;
-                if ((i + 1) * NT <= PSF || tid + i * NT < PSF) {
-                    lds_ptr_t d = (lds_ptr_t)(bufp + wave * 64 + j * PSF + i * NT);
-                    const int ci = chunk * CK + j;
-                    const bool from_x1 = ci < a.C1;
-                    const bool chan_ok = ci < a.Cin;
-                    const unsigned soff = from_x1 ? (unsigned)ci * pb1 : (unsigned)max(ci - a.C1, 0) * pb2;
-                    const unsigned vo = chan_ok ? (from_x1 ? ob1[i] : ob2[i]) : kOOB;
-                    if (from_x1) lds_dma4(r1, d, vo, soff);
-                    else lds_dma4(r2, d, vo, soff);
-                }
+        if constexpr (!GENERIC) {
+            st.stage_full_piece(chunk, bufp, q, cs);
+        } else if (q < NPB_F) {
+            const int j = q / NPOSF, i = q % NPOSF;
+            if (!st.dbg_no_patch(chunk) && ((i + 1) * NT <= PSF || tid + i * NT < PSF)) {
+                lds_ptr_t d = (lds_ptr_t)(bufp + wave * 64 + j * PSF + i * NT);
+                const int ci = chunk * CK + j;
+                const bool from_x1 = ci < a.C1;
+                const bool chan_ok = ci < a.Cin;
+                const unsigned soff = from_x1 ? (unsigned)ci * pb1 : (unsigned)max(ci - a.C1, 0) * pb2;
+                const unsigned vo = chan_ok ? (from_x1 ? ob1[i] : ob2[i]) : kOOB;
+                if (from_x1) lds_dma4(r1, d, vo, soff);
+                else lds_dma4(r2, d, vo, soff);
             }
         } else {
-            stage_weight_piece(chunk, bufp, q - NPB_F);
-        }
-    };
-    auto stage_up_piece = [&](int chunk, float* bufp, int q) {
-#ifdef WMD_STAMPS
-        if ((a.dbg_mode & 8) && q < NPB_L && chunk > c_begin_dbg + 1) return;
-#endif
-        if (q < NPB_L) {
-            if (X4 && x4) {
-                if (q < NPL4 && ((q + 1) * NT * 4 <= CK * PSL || (wave * 64 + q * NT) * 4 < CK * PSL))
-                    lds_dma16(r1, (lds_ptr_t)(bufp + (wave * 64 + q * NT) * 4), obL[q], (unsigned)(chunk * CK) * pb1);
-            } else if ((q + 1) * NT <= CK * PSL || wave * 64 + q * NT < CK * PSL)
-                lds_dma4(r1, (lds_ptr_t)(bufp + wave * 64 + q * NT), obL[q], (unsigned)(chunk * CK) * pb1);
-        } else {
-            stage_weight_piece(chunk, bufp, q - NPB_L);
+            st.stage_weight_piece(chunk, bufp, q - NPB_F);
         }
     };
 
     const int c_begin = ks * cps;
     const int c_end = skip ? c_begin : min(c_begin + cps, a.nchunks);
     WMD_STAMP(4);   // descriptors, weight offsets
-    if (c_begin < c_end) {
-        if (is_up(c_begin)) {
-            static_for<NPB_L + T::NAV>([&](auto qc) { stage_up_piece(c_begin, lds, decltype(qc)::value); });
-        } else {
-            const ChunkSrc cs0 = chunk_src(c_begin);
-            static_for<NPB_F + T::NAV>([&](auto qc) { stage_full_piece(c_begin, lds, decltype(qc)::value, cs0); });
-        }
-    }
+    st.template issue_first<NPB_F>(c_begin, c_end, stage_full_piece);
     const int co = by * 32 + (lane & 31);
     const float bias_v = (a.bias && co < a.Cout) ? a.bias[co] : 0.f;   // requested now, used in the epilogue
 
@@ -448,7 +201,7 @@ __global__ __launch_bounds__(WN * 128, 2) void conv_wino32_kernel(const ConvKArg
             const float* psrc = bufp + (UP ? pbL : pbF);
             const float* wsrc = bufp + wbase;
             ChunkSrc csn;
-            if constexpr (NEXT == 1) csn = chunk_src(c + 1);
+            if constexpr (NEXT == 1) csn = st.chunk_src(c + 1);
             // The input transform in packed fp32 (v_pk_add_f32, two adds per lane per instruction): fp32 MFMA and the vector ALU are
             // the same hardware, every VALU instruction between two MFMAs comes out of the matrix rate
             // (tools/probes/mfma32_issue_probe.hip: one packed add costs what one plain add costs).  Pairs run along patch columns.
@@ -544,7 +297,7 @@ __global__ __launch_bounds__(WN * 128, 2) void conv_wino32_kernel(const ConvKArg
                     constexpr int qb = q0 < NPIECES ? q0 : NPIECES, qe = q1 < NPIECES ? q1 : NPIECES;
                     static_for<qe - qb>([&](auto qc) {
                         constexpr int q = qb + decltype(qc)::value;
-                        if constexpr (NEXT == 2) stage_up_piece(c + 1, nbufp, q);
+                        if constexpr (NEXT == 2) st.stage_up_piece(c + 1, nbufp, q);
                         else stage_full_piece(c + 1, nbufp, q, csn);
                     });
                 }
@@ -554,24 +307,7 @@ __global__ __launch_bounds__(WN * 128, 2) void conv_wino32_kernel(const ConvKArg
             });
             __syncthreads();   // next buffer landed (vmcnt(0) precedes the barrier), this one is released
         };
-        // Two plain loops (upsampled chunks first, then the rest) with peeled last iterations: one body per loop keeps the
-        // accumulators in place across the back edge (a single loop that switches between body variants makes the register
-        // allocator rotate the 128 accumulator registers through copies and spills).
-        const int up_end = min(c_end, max(c_begin, upl ? a.C1 / CK : 0));
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        int c = c_begin;
-        if constexpr (!GENERIC) {
-            for (; c + 1 < up_end; ++c) chunk_body(c, std::true_type{}, I2{});
-            if (c < up_end) {
-                if (up_end < c_end) chunk_body(c, std::true_type{}, I1{});
-                else chunk_body(c, std::true_type{}, I0{});
-                ++c;
-            }
-        }
-        for (; c + 1 < c_end; ++c) chunk_body(c, std::false_type{}, I1{});
-        if (c < c_end) chunk_body(c, std::false_type{}, I0{});
+        w32_walk_chunks<!GENERIC>(c_begin, c_end, st.up_end(c_begin, c_end), chunk_body);
 
         WMD_STAMP(7);   // main loop done
         // ---- epilogue -------------------------------------------------------------------------------------------------
@@ -709,11 +445,7 @@ __global__ __launch_bounds__(WN * 128, 2) void conv_wino32_kernel(const ConvKArg
 #ifdef WMD_STAMPS
         if ((a.dbg_mode & 2) && final_out) act_sel = WMD_ACT_NONE;
 #endif
-        if (act_sel < 0) finish(std::integral_constant<int, -1>{});
-        else if (act_sel == WMD_ACT_ELU) finish(std::integral_constant<int, WMD_ACT_ELU>{});
-        else if (act_sel == WMD_ACT_LEAKY) finish(std::integral_constant<int, WMD_ACT_LEAKY>{});
-        else if (act_sel == WMD_ACT_SIGMOID) finish(std::integral_constant<int, WMD_ACT_SIGMOID>{});
-        else finish(std::integral_constant<int, WMD_ACT_NONE>{});
+        w32_act_dispatch(act_sel, finish);
         WMD_STAMP(10);   // stores issued
         if (wt)   // (uniform) the last K-slice block of this (tile, slab) to arrive sums the slices and writes the final tile
             splitk_ticket_finish<WN * 128, TH, TW, 32, MASKED>(a, reinterpret_cast<int*>(lds + T::LDS_FLOATS + T::TAB_FLOATS) + 8, tick, ks_n, b, y0, x0, by * 32);

@@ -148,6 +148,7 @@ __global__ __launch_bounds__(256) void wino44_input_kernel(const W44Args a) {
         const float* src = op1 ? a.x1 + ((size_t)b * a.C1 + ch) * a.H * a.W : a.x2 + ((size_t)b * a.C2 + ch) * a.H * a.W;
         int ro[6], co[6];
         // padded coordinate g in [-1, n + 3]: beyond n only discarded outputs of a ragged tile are reached (read 0)
+        // (not pad_fold, wmd_internal.h: that one clears a flag and returns an in-range pixel; this one answers -1 for "reads 0", also beyond n)
         auto fold = [&](int g, int n) {
             const int refl = g < 0 ? -g : (g >= n ? 2 * n - 2 - g : g);
             const int clam = min(max(g, 0), n - 1);

@@ -38,15 +38,6 @@ namespace wmd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <class F, int... I>
-__device__ __forceinline__ void hc_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void hc_static_for(F&& f) {
-    hc_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains vmcnt -- i.e. every global load in
 // flight, including the chunks requested AHEAD: with it a deeper prefetch changes nothing (measured: PD 1 / 2 / 4 = 33.7 / 32.9 /
 // 33.9 us) and a lone block still takes 16 x 0.94 us for 16 x 0.33 us of MFMA work.  The staged chunks travel global -> registers
@@ -197,13 +188,13 @@ __device__ __forceinline__ void head_chain_body(const HeadChainArgs& a, float* l
 
     chain_fetch<T, KC, LLX>(wreg[0], xreg[0], lreg[0], w1, a.ll_wp1, xb, 0, tid, pix0, plane);
     chain_commit<T, KC, LLX>(wreg[0], xreg[0], lreg[0], lds, tid);
-    hc_static_for<PD>([&](auto kc) __attribute__((always_inline)) {      // chunks 1 .. PD -> register sets 1 .. PD-1, 0
+    static_for<PD>([&](auto kc) __attribute__((always_inline)) {      // chunks 1 .. PD -> register sets 1 .. PD-1, 0
         constexpr int k = decltype(kc)::value + 1;
         if (k < T::NCH) chain_fetch<T, KC, LLX>(wreg[k % PD], xreg[k % PD], lreg[k % PD], w1, a.ll_wp1, xb, k, tid, pix0, plane);
     });
     hc_barrier();
     for (int c0 = 0; c0 < T::NCH; c0 += PD) {
-        hc_static_for<PD>([&](auto dc) __attribute__((always_inline)) {
+        static_for<PD>([&](auto dc) __attribute__((always_inline)) {
             constexpr int d = decltype(dc)::value, dn = (d + 1) % PD;   // register sets of chunk c (free: committed an iteration ago) and c + 1
             const int c = c0 + d;                                       // (NCH % PD == 0: c < NCH)
             const float* ws = lds + (c & (T::NBUF - 1)) * BUF;

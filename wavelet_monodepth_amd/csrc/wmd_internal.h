@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/wmd.h"
 
 namespace wmd {
@@ -76,6 +78,31 @@ __device__ __forceinline__ bool pad_coord(int& g, int n, int pad_mode) {
         if (g < 0 || g >= n) return false;
     }
     return true;
+}
+
+// The same map branch-free, for code every block of a launch runs at the same moment (the 32x32x2 Winograd kernels' offset
+// prologues: nothing hides them, and pad_coord's switch per coordinate with short-circuit tests cost 16 k cycles per block on
+// L14, cycle stamps): the pad mode is uniform, everything is a select.  Returns the source coordinate of padded coordinate g in
+// [-1, n] and clears `ok` on a zero-pad miss; a coordinate beyond the ring (tile overhang) gives some in-range pixel that is
+// never stored.
+__host__ __device__ __forceinline__ int pad_fold(int pad_mode, int g, int n, int& ok) {
+    const int refl = g < 0 ? -g : (g >= n ? 2 * n - 2 - g : g);
+    const int clam = min(max(g, 0), n - 1);
+    ok &= (int)(pad_mode != WMD_PAD_ZERO) | (int)(g == clam);
+    const int r = pad_mode == WMD_PAD_REFLECT ? refl : clam;
+    return min(max(r, 0), n - 1);
+}
+
+// compile-time loop: f(integral_constant<int, I>) for I = 0 .. N-1, expanded by the front end (a `#pragma unroll` loop over
+// the MFMA groups with the piece test inside exceeds the optimizer's full-unroll budget, and a rolled loop would index the
+// accumulators at run time)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 // Order-preserving float <-> uint32 key: unsigned order of the keys is float order of the values, with -0 < +0 (and NaNs
