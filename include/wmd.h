@@ -71,24 +71,31 @@ long wmd_profile_end(char* buf, size_t cap);
  *   yl [N,h,w], yh [N,3,h,w] (LH,HL,HH)  ->  out [N,2h,2w]
  *   if disp != NULL also writes disp = out*disp_scale, clamped to [0,1] when clamp01 != 0
  *   (depth_decoder.py:166 `clamp(yl / 2**(i-1), 0, 1)`; NYUv2 decoder: scale only).
- *   N = batch*channels (channels is 1 everywhere in the reference).                   */
+ *   N = batch*channels (channels is 1 everywhere in the reference).
+ *   Alignment: with an even w the kernel loads float2 and stores float4 through these pointers, so yl and yh must be
+ *   8-byte and out and disp 16-byte aligned (WMD_ERR_BAD_ARG otherwise, nothing launched); an odd w runs a scalar
+ *   kernel and needs only the 4 bytes of a float.  Tensors are dense: no strides.       */
 int wmd_idwt_haar_fwd(const float* yl, const float* yh, float* out, float* disp,
                       int N, int h, int w, float disp_scale, int clamp01, void* stream);
 
 /* Adjoint of the above.  d_out [N,2h,2w] (may be NULL = zero), d_disp [N,2h,2w] (may be NULL);
  * `out` is the forward result (needed for the clamp mask when d_disp != NULL && clamp01).
- * Writes d_yl [N,h,w] and d_yh [N,3,h,w].                                              */
+ * Writes d_yl [N,h,w] and d_yh [N,3,h,w].
+ * Alignment: d_out, d_disp and out are read as float2 and must be 8-byte aligned whatever w is (WMD_ERR_BAD_ARG
+ * otherwise, nothing launched); d_yl and d_yh are stored float by float.                */
 int wmd_idwt_haar_bwd(const float* d_out, const float* d_disp, const float* out,
                       float* d_yl, float* d_yh, int N, int h, int w,
                       float disp_scale, int clamp01, void* stream);
 
 /* DWT(J=1, wave="haar", mode="reflect"/"zero") on even H,W (the only case the reference hits,
  * NYUv2/train.py:258 on 240x320 depth): x [N,2h,2w] -> yl [N,h,w], yh [N,3,h,w].
- * Call J times for a J-level transform (yh list is fine -> coarse).                    */
+ * Call J times for a J-level transform (yh list is fine -> coarse).
+ * Alignment: x is read as float2 and must be 8-byte aligned (WMD_ERR_BAD_ARG otherwise); yl, yh: 4 bytes.   */
 int wmd_dwt_haar_fwd(const float* x, float* yl, float* yh, int N, int h, int w, void* stream);
 /* The same analysis step for ANY input size H x W (mode="reflect" of pytorch_wavelets' DWTForward, NYUv2/train.py:258):
  * an odd axis is extended by one reflected sample on the right / bottom (x[N] = x[N-2]) before the stride-2 filter
- * pair, so yl [N,ceil(H/2),ceil(W/2)], yh [N,3,ceil(H/2),ceil(W/2)].  An odd axis needs >= 2 samples.                */
+ * pair, so yl [N,ceil(H/2),ceil(W/2)], yh [N,3,ceil(H/2),ceil(W/2)].  An odd axis needs >= 2 samples.  Scalar loads and
+ * stores: every pointer needs only a float's 4-byte alignment.                                                        */
 int wmd_dwt_haar_reflect_fwd(const float* x, float* yl, float* yh, int N, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------ *
@@ -270,7 +277,8 @@ int wmd_conv_wino44_supported(const wmd_conv_args* args);
 size_t wmd_conv_wino44_workspace_floats(const wmd_conv_args* args);
 int wmd_conv_wino44_fwd(const wmd_conv_args* args, void* stream);
 
-/* dz = dy * act'(y)  (y = the activation OUTPUT saved by the forward). In place allowed. */
+/* dz = dy * act'(y)  (y = the activation OUTPUT saved by the forward). In place allowed.  Scalar loads and stores: 4-byte
+ * alignment suffices.                                                                     */
 int wmd_act_bwd(const float* dy, const float* y, float* dz, size_t n, int act, float slope, void* stream);
 
 typedef struct {

@@ -10,6 +10,7 @@
 // (12 B when the normalised `disp` plane is written too).  Each thread handles two horizontally
 // adjacent coefficient positions: float2 coefficient loads, float4 output stores, fully coalesced.
 #include <algorithm>
+#include <cstdint>
 #include "wmd_internal.h"
 
 namespace wmd {
@@ -138,6 +139,9 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __rest
     }
 }
 
+// the vector kernels load float2 and store float4 through the caller's pointers (include/wmd.h states the contract)
+static inline bool aligned_to(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+
 static inline int grid_for(size_t work, int block) {
     size_t b = (work + block - 1) / block;
     return (int)std::min<size_t>(std::max<size_t>(b, 1), (size_t)kNumCU * 8);
@@ -151,9 +155,11 @@ extern "C" int wmd_idwt_haar_fwd(const float* yl, const float* yh, float* out, f
                                  float disp_scale, int clamp01, void* stream) {
     if (!yl || !yh || !out) return fail(WMD_ERR_BAD_ARG, "wmd_idwt_haar_fwd: null pointer");
     if (N < 0 || h <= 0 || w <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_idwt_haar_fwd: N=%d h=%d w=%d", N, h, w);
+    if ((w & 1) == 0 && !(aligned_to(yl, 8) && aligned_to(yh, 8) && aligned_to(out, 16) && aligned_to(disp, 16)))
+        return fail(WMD_ERR_BAD_ARG, "wmd_idwt_haar_fwd: even w needs yl, yh 8-byte and out, disp 16-byte aligned");
     if (N == 0) return WMD_OK;
     // 8 B moved and 4 FLOP per output pixel (reference op model depth_decoder.py:373), 12 B with disp
-    ProfScope prof("idwt_haar_fwd_kernel", 16.0 * N * h * w, (disp ? 48.0 : 32.0) * N * h * w, (hipStream_t)stream);
+    ProfScope prof((w & 1) ? "idwt_haar_fwd_scalar_kernel" : "idwt_haar_fwd_kernel", 16.0 * N * h * w, (disp ? 48.0 : 32.0) * N * h * w, (hipStream_t)stream);
     if ((w & 1) == 0) {
         const size_t work = (size_t)N * h * (w / 2);
         hipLaunchKernelGGL(idwt_haar_fwd_kernel, dim3(grid_for(work, 256)), dim3(256), 0, (hipStream_t)stream, yl, yh,
@@ -171,6 +177,8 @@ extern "C" int wmd_idwt_haar_bwd(const float* d_out, const float* d_disp, const 
     if (!d_yl || !d_yh) return fail(WMD_ERR_BAD_ARG, "wmd_idwt_haar_bwd: null output pointer");
     if (d_disp && clamp01 && !out) return fail(WMD_ERR_BAD_ARG, "wmd_idwt_haar_bwd: clamp mask needs `out`");
     if (N < 0 || h <= 0 || w <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_idwt_haar_bwd: N=%d h=%d w=%d", N, h, w);
+    if (!(aligned_to(d_out, 8) && aligned_to(d_disp, 8) && aligned_to(out, 8)))
+        return fail(WMD_ERR_BAD_ARG, "wmd_idwt_haar_bwd: d_out, d_disp and out must be 8-byte aligned");
     if (N == 0) return WMD_OK;
     const size_t work = (size_t)N * h * w;
     ProfScope prof("haar_analysis_kernel", 16.0 * work, (d_out && d_disp ? 64.0 : 32.0) * work, (hipStream_t)stream);
@@ -182,6 +190,7 @@ extern "C" int wmd_idwt_haar_bwd(const float* d_out, const float* d_disp, const 
 extern "C" int wmd_dwt_haar_fwd(const float* x, float* yl, float* yh, int N, int h, int w, void* stream) {
     if (!x || !yl || !yh) return fail(WMD_ERR_BAD_ARG, "wmd_dwt_haar_fwd: null pointer");
     if (N < 0 || h <= 0 || w <= 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_dwt_haar_fwd: N=%d h=%d w=%d", N, h, w);
+    if (!aligned_to(x, 8)) return fail(WMD_ERR_BAD_ARG, "wmd_dwt_haar_fwd: x must be 8-byte aligned");
     if (N == 0) return WMD_OK;
     const size_t work = (size_t)N * h * w;
     ProfScope prof("haar_analysis_kernel", 16.0 * work, 32.0 * work, (hipStream_t)stream);

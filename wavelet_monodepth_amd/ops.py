@@ -39,6 +39,15 @@ def _c(t):
     return t if t is None or t.is_contiguous() else t.contiguous()
 
 
+def _ca(t, align=16):
+    """_c for the entry points that load and store vectors through the pointer (include/wmd.h: the Haar transforms): a
+    contiguous view whose storage offset leaves data_ptr() off an `align`-byte boundary is copied too"""
+    if t is None:
+        return None
+    t = _c(t)
+    return t if t.data_ptr() % align == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 # ---------------------------------------------------------------------------------------------
 # switches (environment, read once at import; tests and tools may assign the globals afterwards)
 # ---------------------------------------------------------------------------------------------
@@ -1288,8 +1297,7 @@ class _FusedLevelFn(torch.autograd.Function):
         # adjoint of the synthesis: d(out) + d(disp) through the clamp -> d(low-pass input), d(yh)
         d_lo = torch.empty((B, 1, H, W), device=x.device, dtype=torch.float32)
         d_hi = torch.empty((B, 1, 3, H, W), device=x.device, dtype=torch.float32)
-        d_out = _c(d_out) if d_out is not None else None
-        d_disp = _c(d_disp) if d_disp is not None else None
+        d_out, d_disp = _ca(d_out), _ca(d_disp)
         if d_out is None and d_disp is None:
             d_lo.zero_()
             d_hi.zero_()
@@ -1326,7 +1334,7 @@ class _IdwtFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, yl, yh, disp_scale, clamp01, want_disp):
         l = _lib.lib()
-        yl, yh = _c(yl), _c(yh)
+        yl, yh = _ca(yl), _ca(yh)
         B, Cc, h, w = yl.shape
         out = torch.empty((B, Cc, 2 * h, 2 * w), device=yl.device, dtype=torch.float32)
         disp = torch.empty_like(out) if want_disp else None
@@ -1345,8 +1353,8 @@ class _IdwtFn(torch.autograd.Function):
         disp_scale, clamp01, want_disp, sl, sh = ctx.cfg
         d_yl = torch.empty(sl, device=out.device, dtype=torch.float32)
         d_yh = torch.empty(sh, device=out.device, dtype=torch.float32)
-        d_out = _c(d_out) if d_out is not None else None
-        d_disp = _c(d_disp) if (want_disp and d_disp is not None) else None
+        d_out = _ca(d_out)
+        d_disp = _ca(d_disp) if want_disp else None
         check(l.wmd_idwt_haar_bwd(ptr(d_out), ptr(d_disp), ptr(out), ptr(d_yl), ptr(d_yh), sl[0] * sl[1], sl[2], sl[3],
                                   float(disp_scale), int(clamp01), current_stream()), "wmd_idwt_haar_bwd")
         return d_yl, d_yh, None, None, None
@@ -1368,7 +1376,7 @@ def dwt_haar(x, J=1):
     ceil(size/2) coefficients.  The reference only uses it on ground truth (no gradient, NYUv2/train.py:289)."""
     _require_gpu(x)
     l = _lib.lib()
-    ll = _c(x.detach())
+    ll = _ca(x.detach())
     yh = []
     for _ in range(J):
         B, Cc, H, W = ll.shape
