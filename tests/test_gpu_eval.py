@@ -80,8 +80,51 @@ def test_kitti_chain_vs_oracle(dev, B, h, w, H, W, mode):
         np.testing.assert_allclose(err[b], np.array(ref, dtype=np.float64), rtol=2e-5, atol=1e-7)   # resampling rounding only
 
 
+def _middle_keys(vals):
+    """Bit patterns of the two middle order statistics of an even-sized float32 set."""
+    s = np.sort(vals)
+    return s[len(s) // 2 - 1: len(s) // 2 + 1].view(np.uint32)
+
+
+def _median_cases():
+    """(name, gt [B,40,50], disp [B,40,50]) for what the three-level select (bits 31..21, 20..10, 9..0 of the float patterns)
+    can get wrong beyond the counts below; valid pixels are scattered over the plane, the rest is zero (masked out)."""
+    H, W = 40, 50
+
+    def plane(tag, vals):
+        p = np.zeros(H * W, np.float32)
+        p[np.argsort(u(tag + "pos", (H * W,), 0.0, 1.0))[:len(vals)]] = vals
+        return p.reshape(H, W)
+
+    const = np.full((1, H, W), 0.1, np.float32)
+    # ranks per image: three valid counts (odd, even, none) in one call, over predictions that vary too
+    per_image = np.stack([plane("pi%d" % n, u("piv%d" % n, (n,), 1.0, 70.0)) for n in (1001, 64, 0)])
+    # an even count whose middle values lie in different level-0 bins: the upper one is the smallest key above the prefix
+    far = np.concatenate([u("lo", (500,), 0.9, 1.1), u("hi", (500,), 55.0, 65.0)])
+    k = _middle_keys(far)
+    assert k[0] >> 21 != k[1] >> 21
+    # ... are adjacent floats: one 22-bit prefix, the upper one in the next occupied level-2 bin
+    a = np.float32(20.0)
+    near = np.concatenate([u("below", (31,), 1.0, 10.0), [a, np.nextafter(a, np.float32(np.inf))], u("above", (31,), 30.0, 70.0)]).astype(np.float32)
+    k = _middle_keys(near)
+    assert k[0] >> 10 == k[1] >> 10 and k[0] + 1 == k[1]
+    return [("per_image", per_image, u("pid", (3, H, W), 0.01, 0.3)),
+            ("level0_crossing", plane("far", far)[None], const),
+            ("adjacent_floats", plane("near", near)[None], u("nd", (1, H, W), 0.01, 0.3)),
+            ("all_equal", np.full((1, H, W), 7.5, np.float32), const)]   # no next bin and no key above the prefix
+
+
 def test_kitti_chain_median_is_exact_order_statistic(dev):
-    """Radix select == np.median, bit for bit, for odd and even counts and with ties."""
+    """Radix select == np.median, bit for bit, for odd and even counts and with ties; then _median_cases."""
+    for name, gt, disp in _median_cases():
+        _, ratios, nv = ev.kitti_metrics(g(disp, dev), g(gt, dev), eval_split="benchmark")
+        for b in range(gt.shape[0]):
+            mask = gt[b] > 0
+            assert int(nv[b]) == mask.sum(), name
+            if not mask.any():
+                assert np.isnan(float(ratios[b])), name                          # both medians are 0
+                continue
+            assert float(ratios[b]) == np.median(gt[b][mask]) / np.median(np.float32(1) / disp[b][mask]), (name, b)
     for n_valid in (1, 2, 5, 64, 1001):
         H, W = 40, 50
         gt = np.zeros((1, H, W), np.float32)

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdint>
 #include "wmd_internal.h"
+#include "wmd_select.h"
 
 namespace wmd {
 
@@ -50,16 +51,13 @@ __global__ __launch_bounds__(256) void dbe_prep_kernel(const float* __restrict__
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int nseg = Wp >> 1, items = H * nseg;
     const size_t plane = (size_t)H * W;
-    unsigned kmin = 0xFFFFFFFFu, kmax = 0u, ngt = 0;
+    KeyRange<true> kr;
+    unsigned ngt = 0;
     for (int it = blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += gridDim.x * 4) {
         const int r = it / nseg, sg = it - r * nseg, c = sg * 64 + lane;
         const bool in = c < W;
         const float v = in ? pred[b * plane + (size_t)r * W + c] : 0.f;
-        if (v != 0.f && v == v) {
-            const unsigned k = order_key(v);
-            kmin = k < kmin ? k : kmin;
-            kmax = k > kmax ? k : kmax;
-        }
+        if (v != 0.f && v == v) kr.take(order_key(v));
         const bool g = in && gt[b * plane + (size_t)r * W + c] != 0;
         const unsigned long long bits = __ballot(g);
         if (lane == 0) {
@@ -69,16 +67,12 @@ __global__ __launch_bounds__(256) void dbe_prep_kernel(const float* __restrict__
             ngt += __popcll(bits);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned a = __shfl_xor(kmin, o), c = __shfl_xor(kmax, o);
-        kmin = a < kmin ? a : kmin;
-        kmax = c > kmax ? c : kmax;
-    }
+    kr.wave();                 // a wave publishes for itself: its lane 0 also holds the edge count of its rows
     if (lane == 0) {
         unsigned* st = state + (size_t)b * DBE_STATE;
-        if (kmin != 0xFFFFFFFFu) {
-            atomicMin(&st[0], kmin);
-            atomicMax(&st[1], kmax);
+        if (kr.mn != 0xFFFFFFFFu) {
+            atomicMin(&st[0], kr.mn);
+            atomicMax(&st[1], kr.mx);
         }
         if (ngt) atomicAdd(&st[3], ngt);
     }

@@ -9,10 +9,9 @@
 //   eval_prepare_kernel   one pass over the ground-truth grid: bilinear resample of the low-resolution disparity
 //                         (half-pixel centres, edge clamp = cv2.INTER_LINEAR = F.interpolate(align_corners=False)),
 //                         reciprocal, mask; masked-out pixels are stored as -1 in both planes; per-image counts.
-//   eval_hist/scan/next   np.median of the valid pixels of a plane = mean of the two middle order statistics: radix
-//                         select on the float bit patterns (positive floats order like their uint32 patterns; the -1
-//                         sentinels order above every valid value): three multi-block histogram levels (11+11+10
-//                         bits) + one count/min pass for the upper middle value.
+//   eval_select_kernel    np.median of the valid pixels of a plane = mean of the two middle order statistics: the radix
+//                         select of wmd_select.h on the float bit patterns, three multi-block histogram levels (11+11+10
+//                         bits); eval_median_finish_kernel resolves both statistics from the histograms.
 //   eval_metrics_kernel   ratio scaling + clamp + the seven (KITTI) / six (NYUv2) error sums, fp64 accumulation, up to 64
 //                         blocks per image + a deterministic finish.
 // All three are HBM-bound streaming kernels: 8 + 4 B read and 8 B written per ground-truth pixel in prepare, 4 B per
@@ -21,6 +20,7 @@
 #include <cmath>
 #include <cstdint>
 #include "wmd_internal.h"
+#include "wmd_select.h"
 
 namespace wmd {
 
@@ -70,128 +70,31 @@ __global__ void eval_prepare_kernel(const float* __restrict__ disp, const float*
 }
 
 // np.median of the n = count[b] valid values of a plane = 0.5 * (v[k0] + v[k1]), k0 = (n-1)/2, k1 = n/2 (0-based order
-// statistics).  v[k0] by a three-level radix select over the float bit patterns (11 + 11 + 10 bits), every level a
-// multi-block histogram pass (LDS sub-histograms flushed with global atomics) followed by a one-block scan that picks
-// the bin holding the rank; v[k1] from one more pass: it is v[k0] again when enough values are <= v[k0], else the
-// smallest value above it.  Four streaming passes over the plane instead of sorting it.
-constexpr int EV_BINS = 2048;
-struct EvSel {            // per (image, plane) selection state, lives in the workspace
-    unsigned prefix;      // key bits decided so far (right-aligned)
-    unsigned rank;        // rank still to be resolved inside the current prefix
-    unsigned count_le;    // final pass: #keys <= key(v[k0])
-    unsigned min_gt;      // final pass: smallest key > key(v[k0])
+// statistics), by the radix select of wmd_select.h over the raw bit patterns: valid values are positive, which order like
+// their patterns, and the -1 sentinels order above them.  An item is (plane, image): plane which * B + b of the 2 B masked
+// planes, state and median b * 2 + which; its rank comes from the image's count on the device.
+struct EvKey {
+    static __device__ __forceinline__ unsigned of(float v) { return __float_as_uint(v); }
 };
 
-__device__ __forceinline__ const unsigned* ev_plane(const float* pd, const float* gm, int which, int b, size_t plane) {
-    return reinterpret_cast<const unsigned*>((which == 0 ? pd : gm) + (size_t)b * plane);
-}
+__device__ __forceinline__ unsigned ev_rank(int n) { return n > 0 ? (unsigned)(n - 1) / 2u : 0u; }
 
-// level 0: bits 31..21, level 1: bits 20..10, level 2: bits 9..0
-__global__ __launch_bounds__(256) void eval_hist_kernel(const float* __restrict__ pd, const float* __restrict__ gm,
-                                                        const EvSel* __restrict__ sel, unsigned* __restrict__ hist,
-                                                        size_t plane, int level) {
+// grid (blocks, 2, B)
+template <int LEVEL>
+__global__ __launch_bounds__(SEL_THREADS) void eval_select_kernel(const float* __restrict__ planes, const int* __restrict__ count,
+                                                                 unsigned* __restrict__ state, size_t plane) {
     const int which = blockIdx.y, b = blockIdx.z;
-    const unsigned* v = ev_plane(pd, gm, which, b, plane);
-    const int shift = level == 0 ? 21 : (level == 1 ? 10 : 0);
-    const unsigned mask = level == 2 ? 1023u : 2047u;
-    const int hi_shift = level == 0 ? 32 : (level == 1 ? 21 : 10);
-    const unsigned prefix = sel[b * 2 + which].prefix;
-    __shared__ unsigned lh[EV_BINS];
-    for (int i = threadIdx.x; i < EV_BINS; i += blockDim.x) lh[i] = 0;
-    __syncthreads();
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (size_t)gridDim.x * blockDim.x) {
-        const unsigned k = v[i];
-        if ((unsigned)((unsigned long long)k >> hi_shift) == prefix) atomicAdd(&lh[(k >> shift) & mask], 1u);
-    }
-    __syncthreads();
-    unsigned* gh = hist + (size_t)(b * 2 + which) * EV_BINS;
-    for (int i = threadIdx.x; i < EV_BINS; i += blockDim.x)
-        if (lh[i]) atomicAdd(&gh[i], lh[i]);
+    sel_pass<LEVEL, EvKey>(planes + ((size_t)which * gridDim.z + b) * plane, state + (size_t)(b * 2 + which) * SEL_STATE, plane,
+                           ev_rank(count[b]));
 }
 
-// one block per (plane, image): find the bin that holds the rank, descend, clear the histogram for the next level
-__global__ __launch_bounds__(256) void eval_scan_kernel(EvSel* __restrict__ sel, unsigned* __restrict__ hist,
-                                                        const int* __restrict__ count, int level) {
-    const int which = blockIdx.x, b = blockIdx.y;
-    EvSel* st = sel + b * 2 + which;
-    unsigned* gh = hist + (size_t)(b * 2 + which) * EV_BINS;
-    __shared__ unsigned part[256];
-    __shared__ unsigned s_bin, s_rank;
-    const int n = count[b];
-    const unsigned rank = level == 0 ? (n > 0 ? (unsigned)(n - 1) / 2u : 0u) : st->rank;
-    // 8 bins per thread
-    unsigned loc[8], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        loc[j] = gh[threadIdx.x * 8 + j];
-        sum += loc[j];
-    }
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned cum = 0;
-        int t = 0;
-        for (; t < 255; ++t) {
-            if (cum + part[t] > rank) break;
-            cum += part[t];
-        }
-        s_bin = (unsigned)t;      // the thread whose 8 bins hold the rank
-        s_rank = rank - cum;
-    }
-    __syncthreads();
-    if (threadIdx.x == s_bin) {
-        unsigned cum = 0, r = s_rank;
-        int j = 0;
-        for (; j < 7; ++j) {
-            if (cum + loc[j] > r) break;
-            cum += loc[j];
-        }
-        const int bits = level == 2 ? 10 : 11;
-        st->prefix = ((level == 0 ? 0u : st->prefix) << bits) | (unsigned)(threadIdx.x * 8 + j);
-        st->rank = r - cum;
-        st->count_le = 0;
-        st->min_gt = 0xFFFFFFFFu;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) gh[threadIdx.x * 8 + j] = 0;
-}
-
-__global__ __launch_bounds__(256) void eval_next_kernel(const float* __restrict__ pd, const float* __restrict__ gm,
-                                                        EvSel* __restrict__ sel, size_t plane) {
-    const int which = blockIdx.y, b = blockIdx.z;
-    const unsigned* v = ev_plane(pd, gm, which, b, plane);
-    EvSel* st = sel + b * 2 + which;
-    const unsigned key = st->prefix;
-    unsigned le = 0, mn = 0xFFFFFFFFu;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (size_t)gridDim.x * blockDim.x) {
-        const unsigned k = v[i];
-        le += k <= key ? 1u : 0u;
-        mn = (k > key && k < mn) ? k : mn;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        le += __shfl_xor(le, o);
-        const unsigned other = __shfl_xor(mn, o);
-        mn = other < mn ? other : mn;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (le) atomicAdd(&st->count_le, le);
-        atomicMin(&st->min_gt, mn);
-    }
-}
-
-__global__ void eval_median_finish_kernel(const EvSel* __restrict__ sel, const int* __restrict__ count, float* __restrict__ med, int B) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (image, plane)
-    if (i >= B * 2) return;
-    const int n = count[i >> 1];
-    if (n <= 0) {
-        med[i] = 0.f;
-        return;
-    }
-    const EvSel st = sel[i];
-    const unsigned k1 = (unsigned)n / 2u;
-    const float v0 = __uint_as_float(st.prefix);
-    const float v1 = st.count_le > k1 ? v0 : __uint_as_float(st.min_gt);
-    med[i] = 0.5f * (v0 + v1);
+// one block per item; k1 differs from k0 for an even n
+__global__ __launch_bounds__(SEL_THREADS) void eval_median_finish_kernel(const unsigned* __restrict__ state, const int* __restrict__ count,
+                                                                        float* __restrict__ med) {
+    __shared__ unsigned sm[12];
+    const int i = blockIdx.x, n = count[i >> 1];
+    const SelKeys k = sel_resolve(state + (size_t)i * SEL_STATE, ev_rank(n), n > 0 && (n & 1) == 0, sm);
+    if (threadIdx.x == 0) med[i] = n > 0 ? 0.5f * (__uint_as_float(k.at) + __uint_as_float(k.next)) : 0.f;
 }
 
 // out[b][0..8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, log10, n_valid.  Entries < 0 in gm are skipped.
@@ -300,9 +203,9 @@ using namespace wmd;
 
 extern "C" size_t wmd_eval_workspace_floats(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    // two masked planes, [B] counts (int), [B,2] medians, [B,2] selection states, [B,2,2048] histograms
+    // two masked planes, [B] counts (int), [B,2] medians, [B,2] selection states (three histograms each)
     // + [B,64,9] fp64 partial error sums (and one float of slack to align them to 8 bytes)
-    return (size_t)B * H * W * 2 + (size_t)B * 3 + (size_t)B * 2 * 4 + (size_t)B * 2 * 2048 + (size_t)B * 64 * 9 * 2 + 2;
+    return (size_t)B * H * W * 2 + (size_t)B * 3 + (size_t)B * 2 * SEL_STATE + (size_t)B * 64 * 9 * 2 + 2;
 }
 
 extern "C" int wmd_eval_kitti(const wmd_eval_kitti_args* g, void* stream) {
@@ -329,24 +232,34 @@ extern "C" int wmd_eval_kitti(const wmd_eval_kitti_args* g, void* stream) {
     }
     int st = check_launch("eval_prepare_kernel");
     if (st) return st;
+    unsigned* state = reinterpret_cast<unsigned*>(med + 2 * g->B);
+    const size_t state_words = (size_t)g->B * 2 * SEL_STATE;
     if (g->median_scaling) {
-        EvSel* sel = reinterpret_cast<EvSel*>(med + 2 * g->B);
-        unsigned* hist = reinterpret_cast<unsigned*>(sel + 2 * g->B);
-        if (hipMemsetAsync(sel, 0, sizeof(EvSel) * 2 * g->B + sizeof(unsigned) * 2 * EV_BINS * g->B, s) != hipSuccess)
+        if (hipMemsetAsync(state, 0, sizeof(unsigned) * state_words, s) != hipSuccess)
             return fail(WMD_ERR_HIP, "wmd_eval_kitti: hipMemsetAsync failed");
-        const int nblk = (int)std::max<size_t>(1, std::min<size_t>((plane + 4095) / 4096, 64));
-        ProfScope prof("eval_median (4 passes)", 0.0, 4.0 * 4 * 2 * g->B * plane, s);
-        for (int level = 0; level < 3; ++level) {
-            hipLaunchKernelGGL(eval_hist_kernel, dim3(nblk, 2, g->B), dim3(256), 0, s, pd, gm, sel, hist, plane, level);
-            hipLaunchKernelGGL(eval_scan_kernel, dim3(2, g->B), dim3(256), 0, s, sel, hist, count, level);
+        const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((plane + 4095) / 4096, 64)), 2, g->B);
+        const double bytes = 4.0 * 2 * g->B * plane;
+        {
+            ProfScope prof("eval_select_kernel<0>", 0.0, bytes, s);
+            hipLaunchKernelGGL(eval_select_kernel<0>, grid, dim3(SEL_THREADS), 0, s, pd, count, state, plane);
         }
-        hipLaunchKernelGGL(eval_next_kernel, dim3(nblk, 2, g->B), dim3(256), 0, s, pd, gm, sel, plane);
-        hipLaunchKernelGGL(eval_median_finish_kernel, dim3((2 * g->B + 63) / 64), dim3(64), 0, s, sel, count, med, g->B);
+        {
+            ProfScope prof("eval_select_kernel<1>", 0.0, bytes, s);
+            hipLaunchKernelGGL(eval_select_kernel<1>, grid, dim3(SEL_THREADS), 0, s, pd, count, state, plane);
+        }
+        {
+            ProfScope prof("eval_select_kernel<2>", 0.0, bytes, s);
+            hipLaunchKernelGGL(eval_select_kernel<2>, grid, dim3(SEL_THREADS), 0, s, pd, count, state, plane);
+        }
+        {
+            ProfScope prof("eval_median_finish_kernel", 0.0, 0.0, s);
+            hipLaunchKernelGGL(eval_median_finish_kernel, dim3(2 * g->B), dim3(SEL_THREADS), 0, s, state, count, med);
+        }
         st = check_launch("eval_median");
         if (st) return st;
     }
     const int mblk = (int)std::max<size_t>(1, std::min<size_t>((plane + 8191) / 8192, 64));
-    float* after = reinterpret_cast<float*>(reinterpret_cast<unsigned*>(med + 2 * g->B) + (size_t)g->B * 2 * 4 + (size_t)g->B * 2 * EV_BINS);
+    float* after = reinterpret_cast<float*>(state + state_words);
     double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(after) + 7) & ~(uintptr_t)7);
     ProfScope prof("eval_metrics_kernel", 30.0 * g->B * plane, 8.0 * g->B * plane, s);
     hipLaunchKernelGGL(eval_metrics_kernel, dim3(mblk, g->B), dim3(1024), 0, s, pd, gm, med, g->out, partial, plane, g->median_scaling,

@@ -8,22 +8,15 @@
 // wmd_viz_disparity, at most five launches whatever B:
 //   upsample_bilinear_fwd_kernel  the existing resample (wmd_resample.hip), skipped when the size does not change; the map is
 //                                 written once and read by the four passes below
-//   viz_select_kernel<0>          keys = float bits with the sign-flip (ascending like the values); per-image min;
-//                                 histogram of key bits 31..21
-//   viz_select_kernel<1>          every block first finds the bin of level 0 that holds rank k (2048 counts, one scan), then
-//                                 counts bits 20..10 of the keys under that prefix
-//   viz_select_kernel<2>          the same one level down (bits 9..0), and the smallest key ABOVE the 22-bit prefix
-//   viz_colour_kernel<0>          every block resolves the three levels: s[k] exactly; s[k+1] = s[k] when the last bin holds
-//                                 more than the remaining rank, else the next occupied bin of level 2, else that smallest
-//                                 key above the prefix.  numpy's float32 lerp, matplotlib's double division, the table, and
-//                                 four pixels = three dwords per store.
-// No scan kernels and no host reads in between: a block re-derives the prefix from the histograms of the levels above it
-// (8 KB from L2 per level) instead of waiting for a one-block launch to do it once.  Histograms are LDS-private per block
-// and flushed once with global atomics (integer adds: the counts do not depend on the order).
+//   viz_select_kernel<0,1,2>      the three passes of the radix select of wmd_select.h at rank k; keys = float bits with the
+//                                 sign-flip (ascending like the values); level 0 leaves the per-image min
+//   viz_colour_kernel<0>          every block resolves the three levels to s[k] and s[k+1].  numpy's float32 lerp,
+//                                 matplotlib's double division, the table, and four pixels = three dwords per store.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include "wmd_internal.h"
+#include "wmd_select.h"
 
 // numpy and matplotlib round every operation on its own: no fused multiply-add may be formed from their products.  The
 // pragma covers what the front end would fuse; the library is built with the HIP default, under which the back end still
@@ -32,183 +25,32 @@
 
 namespace wmd {
 
-constexpr int VZ_BINS = 2048;
-constexpr int VZ_STATE = 8 + 3 * VZ_BINS;   // uint32 per image: [0] ~min key, [1] ~(smallest key above the prefix), [2] max key, [8..] histograms
-constexpr int VZ_THREADS = 256;
-constexpr size_t VZ_CHUNK = 4 * VZ_THREADS;   // values a block takes per step of the reducing passes
+constexpr int VZ_STATE = SEL_STATE;   // uint32 per image: the selection state, with [2] max key
+constexpr int VZ_THREADS = SEL_THREADS;
 
-struct VzFound {
-    unsigned bin;     // the bin that holds the rank
-    unsigned rem;     // rank inside that bin
-    unsigned count;   // keys in that bin
-    unsigned next;    // the next occupied bin above it (0xFFFFFFFF: none)
+struct VzKey {
+    static __device__ __forceinline__ unsigned of(float v) { return order_key(v); }   // ascending like the values
 };
 
-// All 256 threads: which of the 2048 bins of `gh` holds 0-based rank `rank`.  sm: 12 uint32 of LDS, reusable on return.
-__device__ VzFound vz_find(const unsigned* __restrict__ gh, unsigned rank, unsigned* sm) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned loc[8], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        loc[j] = gh[tid * 8 + j];
-        sum += loc[j];
-    }
-    unsigned inc = sum;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (tid == 0) {
-        sm[4] = VZ_BINS - 1;
-        sm[5] = 0;
-        sm[6] = 0;
-    }
-    if (lane == 63) sm[wave] = inc;
-    __syncthreads();
-    unsigned excl = inc - sum;
-    for (int wv = 0; wv < wave; ++wv) excl += sm[wv];
-    if (rank >= excl && rank - excl < sum) {      // one thread: the counts are a partition of the ranks
-        unsigned cum = 0;
-        int j = 0;
-        for (; j < 7; ++j) {
-            if (cum + loc[j] > rank - excl) break;
-            cum += loc[j];
-        }
-        sm[4] = (unsigned)(tid * 8 + j);
-        sm[5] = rank - excl - cum;
-        sm[6] = loc[j];
-    }
-    __syncthreads();
-    VzFound f;
-    f.bin = sm[4];
-    f.rem = sm[5];
-    f.count = sm[6];
-    unsigned nx = 0xFFFFFFFFu;
-#pragma unroll
-    for (int j = 7; j >= 0; --j)
-        if (loc[j] && (unsigned)(tid * 8 + j) > f.bin) nx = (unsigned)(tid * 8 + j);
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned t = __shfl_xor(nx, o);
-        nx = t < nx ? t : nx;
-    }
-    if (lane == 0) sm[8 + wave] = nx;
-    __syncthreads();
-    f.next = min(min(sm[8], sm[9]), min(sm[10], sm[11]));
-    __syncthreads();
-    return f;
-}
-
-// LEVEL 0: bits 31..21 (+ the min); 1: bits 20..10 under the prefix of level 0; 2: bits 9..0 under the 22-bit prefix (+ the
-// smallest key above that prefix).  grid (blocks, B).
+// one level of the select (wmd_select.h) over image blockIdx.y; grid (blocks, B)
 template <int LEVEL>
 __global__ __launch_bounds__(VZ_THREADS) void viz_select_kernel(const float* __restrict__ x, unsigned* __restrict__ state, size_t plane,
                                                                unsigned rank) {
     const int b = blockIdx.y;
-    const float* v = x + (size_t)b * plane;
-    unsigned* st = state + (size_t)b * VZ_STATE;
-    __shared__ unsigned lh[VZ_BINS];
-    __shared__ unsigned sm[12];
-    for (int i = threadIdx.x; i < VZ_BINS; i += VZ_THREADS) lh[i] = 0;
-    unsigned prefix = 0;
-    if (LEVEL >= 1) {
-        const VzFound f0 = vz_find(st + 8, rank, sm);
-        prefix = f0.bin;
-        if (LEVEL == 2) {
-            const VzFound f1 = vz_find(st + 8 + VZ_BINS, f0.rem, sm);
-            prefix = (prefix << 11) | f1.bin;
-        }
-    }
-    __syncthreads();
-    constexpr int shift = LEVEL == 0 ? 21 : (LEVEL == 1 ? 10 : 0);
-    constexpr unsigned mask = LEVEL == 2 ? 1023u : 2047u;
-    unsigned ext = 0xFFFFFFFFu;   // LEVEL 0: smallest key; LEVEL 2: smallest key whose upper 22 bits are above the prefix
-    auto take = [&](float value) {
-        const unsigned k = order_key(value);
-        if (LEVEL == 0) {
-            atomicAdd(&lh[k >> 21], 1u);
-            ext = k < ext ? k : ext;
-        } else {
-            const unsigned hi = LEVEL == 1 ? (k >> 21) : (k >> 10);
-            if (hi == prefix) atomicAdd(&lh[(k >> shift) & mask], 1u);
-            if (LEVEL == 2 && hi > prefix) ext = k < ext ? k : ext;
-        }
-    };
-    // four independent loads in flight per thread: a chunk is 4 x 256 consecutive values, lane-contiguous in each quarter
-    for (size_t base = (size_t)blockIdx.x * VZ_CHUNK; base < plane; base += (size_t)gridDim.x * VZ_CHUNK) {
-        const size_t i = base + threadIdx.x;
-        if (base + VZ_CHUNK <= plane) {
-            const float a0 = v[i], a1 = v[i + VZ_THREADS], a2 = v[i + 2 * VZ_THREADS], a3 = v[i + 3 * VZ_THREADS];
-            take(a0);
-            take(a1);
-            take(a2);
-            take(a3);
-        } else {
-            for (int j = 0; j < 4; ++j)
-                if (i + j * VZ_THREADS < plane) take(v[i + j * VZ_THREADS]);
-        }
-    }
-    __syncthreads();
-    unsigned* gh = st + 8 + LEVEL * VZ_BINS;
-    for (int i = threadIdx.x; i < VZ_BINS; i += VZ_THREADS)
-        if (lh[i]) atomicAdd(&gh[i], lh[i]);
-    if (LEVEL != 1) {
-        // one atomic per block at most, stored inverted (zero = none yet); a block that cannot improve what it reads sends none
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned t = __shfl_xor(ext, o);
-            ext = t < ext ? t : ext;
-        }
-        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = ext;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned m = min(min(sm[0], sm[1]), min(sm[2], sm[3]));
-            unsigned* dst = &st[LEVEL == 0 ? 0 : 1];
-            if (m != 0xFFFFFFFFu && ~m > *reinterpret_cast<volatile unsigned*>(dst)) atomicMax(dst, ~m);
-        }
-    }
+    sel_pass<LEVEL, VzKey>(x + (size_t)b * plane, state + (size_t)b * VZ_STATE, plane, rank);
 }
 
 // per-image min and max of [B,n] planes, as keys: st[0] = ~min key, st[2] = max key (both zero-initialised)
 __global__ __launch_bounds__(VZ_THREADS) void viz_minmax_kernel(const float* __restrict__ x, unsigned* __restrict__ state, size_t plane) {
     const int b = blockIdx.y;
-    const float* v = x + (size_t)b * plane;
-    unsigned mn = 0xFFFFFFFFu, mx = 0u;
-    auto take = [&](float value) {
-        const unsigned k = order_key(value);
-        mn = k < mn ? k : mn;
-        mx = k > mx ? k : mx;
-    };
-    for (size_t base = (size_t)blockIdx.x * VZ_CHUNK; base < plane; base += (size_t)gridDim.x * VZ_CHUNK) {
-        const size_t i = base + threadIdx.x;
-        if (base + VZ_CHUNK <= plane) {
-            const float a0 = v[i], a1 = v[i + VZ_THREADS], a2 = v[i + 2 * VZ_THREADS], a3 = v[i + 3 * VZ_THREADS];
-            take(a0);
-            take(a1);
-            take(a2);
-            take(a3);
-        } else {
-            for (int j = 0; j < 4; ++j)
-                if (i + j * VZ_THREADS < plane) take(v[i + j * VZ_THREADS]);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned a = __shfl_xor(mn, o), c = __shfl_xor(mx, o);
-        mn = a < mn ? a : mn;
-        mx = c > mx ? c : mx;
-    }
+    KeyRange<true> kr;
+    sel_for_each(x + (size_t)b * plane, plane, [&](size_t, float value) { kr.take(order_key(value)); });
     __shared__ unsigned sm[8];
-    if ((threadIdx.x & 63) == 0) {
-        sm[threadIdx.x >> 6] = mn;
-        sm[4 + (threadIdx.x >> 6)] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        mn = min(min(sm[0], sm[1]), min(sm[2], sm[3]));
-        mx = max(max(sm[4], sm[5]), max(sm[6], sm[7]));
+    kr.block(sm);
+    if (threadIdx.x == 0 && kr.mn != 0xFFFFFFFFu) {      // the block saw at least one value
         unsigned* st = state + (size_t)b * VZ_STATE;
-        if (mn != 0xFFFFFFFFu) {      // the block saw at least one value
-            if (~mn > *reinterpret_cast<volatile unsigned*>(st + 0)) atomicMax(st + 0, ~mn);
-            if (mx > *reinterpret_cast<volatile unsigned*>(st + 2)) atomicMax(st + 2, mx);
-        }
+        sel_publish_min(st + 0, kr.mn);
+        if (kr.mx > *reinterpret_cast<volatile unsigned*>(st + 2)) atomicMax(st + 2, kr.mx);
     }
 }
 
@@ -271,14 +113,8 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_colour_kernel(const float* __r
     nm.flat = false;
     if (MODE == 0) {
         const unsigned* st = state + (size_t)b * VZ_STATE;
-        const VzFound f0 = vz_find(st + 8, rank, sm);
-        const VzFound f1 = vz_find(st + 8 + VZ_BINS, f0.rem, sm);
-        const VzFound f2 = vz_find(st + 8 + 2 * VZ_BINS, f1.rem, sm);
-        const unsigned prefix = (f0.bin << 21) | (f1.bin << 10);
-        const unsigned ka = prefix | f2.bin;
-        unsigned kb = ka;                                        // s[k+1]: the same value while its bin holds rank + 1 too
-        if (rank_next != rank && f2.rem + 1 >= f2.count) kb = f2.next != 0xFFFFFFFFu ? (prefix | f2.next) : ~st[1];
-        const float lo = order_unkey(~st[0]), hi = vz_lerp(order_unkey(ka), order_unkey(kb), g);
+        const SelKeys k = sel_resolve(st, rank, rank_next != rank, sm);     // s[k] and s[k+1]
+        const float lo = order_unkey(~st[0]), hi = vz_lerp(order_unkey(k.at), order_unkey(k.next), g);
         nm.lo_d = (double)lo;
         nm.den_d = (double)hi - (double)lo;
         nm.flat = lo == hi;
@@ -344,21 +180,8 @@ __global__ __launch_bounds__(VZ_THREADS) void viz_normalize_kernel(const float* 
     const unsigned* st = state + (size_t)b * VZ_STATE;
     const float mi = order_unkey(~st[0]), ma = order_unkey(st[2]);
     const float d = ma != mi ? (float)((double)ma - (double)mi) : 1e5f;
-    const float* v = x + (size_t)b * plane;
     float* o = y + (size_t)b * plane;
-    for (size_t base = (size_t)blockIdx.x * VZ_CHUNK; base < plane; base += (size_t)gridDim.x * VZ_CHUNK) {
-        const size_t i = base + threadIdx.x;
-        if (base + VZ_CHUNK <= plane) {
-            const float a0 = v[i], a1 = v[i + VZ_THREADS], a2 = v[i + 2 * VZ_THREADS], a3 = v[i + 3 * VZ_THREADS];
-            o[i] = __fdiv_rn(__fsub_rn(a0, mi), d);
-            o[i + VZ_THREADS] = __fdiv_rn(__fsub_rn(a1, mi), d);
-            o[i + 2 * VZ_THREADS] = __fdiv_rn(__fsub_rn(a2, mi), d);
-            o[i + 3 * VZ_THREADS] = __fdiv_rn(__fsub_rn(a3, mi), d);
-        } else {
-            for (int j = 0; j < 4; ++j)
-                if (i + j * VZ_THREADS < plane) o[i + j * VZ_THREADS] = __fdiv_rn(__fsub_rn(v[i + j * VZ_THREADS], mi), d);
-        }
-    }
+    sel_for_each(x + (size_t)b * plane, plane, [&](size_t i, float value) { o[i] = __fdiv_rn(__fsub_rn(value, mi), d); });
 }
 
 static int vz_blocks(size_t plane, int B, size_t per_block) {
