@@ -176,6 +176,15 @@ typedef struct {
     int out_tile_h, out_tile_w;
 } wmd_conv_args;
 
+/* The contract of this problem.  Every entry point that takes it (wmd_conv_fwd, the bf16 and F(4x4,3x3) families, wmd_conv_dgrad,
+ * wmd_conv_wgrad, the depthwise 3x3 with Cout = 1 and ksize = 3, wmd_sparse_conv with max(B, 1) frames) applies the same rules
+ * before any rule of its own and before any HIP call, and reports the first one violated, in this order:
+ *   B, H, W, C1, Cout >= 1 and C2 >= 0 (WMD_ERR_BAD_SHAPE); ksize 1 or 3 (WMD_ERR_UNSUPPORTED); up1 1 or 2 (WMD_ERR_BAD_ARG);
+ *   even H and W when up1 = 2 (WMD_ERR_BAD_SHAPE); pad_mode a wmd_pad (WMD_ERR_BAD_ARG); act a wmd_act, where the entry has one
+ *   (WMD_ERR_BAD_ARG); H, W >= 2 for a 3x3 filter with REFLECT padding (WMD_ERR_BAD_SHAPE).
+ * None of them reads a pointer.  An entry that launches then needs x1, wp and y, and x2 when C2 > 0 (WMD_ERR_BAD_ARG); the
+ * shape queries (*_supported, *_workspace_floats, wmd_conv_fwd_plan) ignore these four pointers.                                */
+
 /* != 0 when wmd_conv_fwd has a work-list kernel for pixel tiles of tile_h x tile_w */
 int wmd_conv_list_tile_supported(int tile_h, int tile_w);
 
@@ -231,7 +240,8 @@ const char* wmd_conv_config_name(int i);
  * addressing, bias, activation.  wmd_conv_args is reused unchanged: wp = the image of wmd_conv_bf16_pack_weights, wp_wino is
  * ignored, tune_cfg = k > 0 forces entry k-1 of the table below (every entry runs every supported problem), tune_ksplit = k
  * (either sign) forces min(|k|, Cin/16) slices of the Cin reduction, summed in slice order by a second-stage kernel.
- * Supported (everything else WMD_ERR_UNSUPPORTED before any launch; wmd_conv_bf16_supported answers without a HIP call):
+ * Supported, beyond the contract at wmd_conv_args (everything else WMD_ERR_UNSUPPORTED before any launch; wmd_conv_bf16_supported
+ * and wmd_conv_bf16_workspace_floats answer for the problem without a HIP call and without reading x1, x2, wp or y):
  *   ksize = 3; pad ZERO or REFLECT; C1 % 16 == 0, C2 % 16 == 0, Cout % 32 == 0; gate, in_mask, out_mask, out_tiles NULL;
  *   tune_cfg in 0 .. wmd_conv_bf16_num_configs().
  * Packed weight image: bf16 in MFMA fragment order, plane q(w), then for terms = 3 plane q(w - q(w)):
@@ -260,8 +270,9 @@ const char* wmd_conv_bf16_config_name(int i);
  * positions carry its channels), concat with x2, border addressing, bias, activation.  Points 0, +-1, +-2, inf: the rounding
  * error is ~2e-5 of the tensor's scale at 512 input channels (the fused F(2x2,3x3) kernels: 4e-7), which is why wmd_conv_fwd never chooses these
  * kernels by itself: a caller opts in per layer (ops.conv3x3_wino44_nograd, inference only).
- * Supported (everything else WMD_ERR_UNSUPPORTED before any launch; wmd_conv_wino44_supported answers without a HIP call):
- *   ksize = 3; up1 1 or 2; pad ZERO, REFLECT or REPLICATE; any C1, C2, Cout up to 65536; gate, in_mask, out_mask, out_tiles
+ * Supported, beyond the contract at wmd_conv_args (everything else WMD_ERR_UNSUPPORTED before any launch; wmd_conv_wino44_supported
+ * answers without a HIP call):
+ *   ksize = 3; any C1, C2, Cout up to 65536; gate, in_mask, out_mask, out_tiles
  *   NULL; tune_cfg = tune_ksplit = 0 (one configuration; the reduction is never split: x1's channels, then x2's, in one
  *   workgroup -- a launch repeats bit for bit); every tensor and image below 2 GiB.
  * wp = the image of wmd_conv_pack_weights_wino44 for the same (Cout, C1, C2, up1): U = G g G^T computed in double and

@@ -103,7 +103,7 @@ def checks(case):
 # ---- A. wmd_dwconv3x3_fwd / wmd_dwconv3x3_bwd --------------------------------------------------------------------------------------
 PADS = ("zero", "reflect", "replicate")
 DATA, FOLD, WGT = "dwconv_bwd_data_kernel", "conv_dgrad_fold_kernel", "dwconv_bwd_weight_kernel"
-# name -> (B, C1, C2, up1, H, W); C1 >= 1 always: dw_check refuses a null x1 (validate_bwd: C1 <= 0 is a shape error)
+# name -> (B, C1, C2, up1, H, W); C1 >= 1 always: dw_check refuses a null x1 (conv_check_problem: C1 <= 0 is a shape error)
 DW_SMALL = {"6x10_up_skip": (2, 5, 7, 2, 6, 10), "5x7_c19": (1, 19, 0, 1, 5, 7), "4x6_skip_noup": (3, 3, 4, 1, 4, 6), "2x2_up": (1, 3, 0, 2, 2, 2)}
 DW_STRIDE = {"130x128_up_skip": (1, 2, 1, 2, 130, 128), "129x128": (1, 3, 0, 1, 129, 128), "126x128_up_skip": (1, 2, 1, 2, 126, 128)}
 DW_REDUCE = {"3x5_15terms": (1, 3, 0, 1, 3, 5), "9x11_99terms": (1, 2, 2, 1, 9, 11), "7x13_273terms": (3, 2, 2, 1, 7, 13)}

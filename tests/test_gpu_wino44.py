@@ -79,7 +79,7 @@ def test_two_launches_over_a_nan_workspace_are_bit_identical_and_write_everythin
     x1, x2, w, b = [None if v is None else v.to(dev) for v in _operands(B, C1, C2, cout, H, W, up, 5)]
     l = _lib.lib()
     wp = ops.pack_weights_wino44(w, C1, up)
-    a = ops._wino44_args(B, H, W, C1, up, C2, cout, 3, "reflect", "elu", 0.0)
+    a = ops._conv_args(B, H, W, C1, up, C2, cout, 3, "reflect", "elu", 0.0)
     n = l.wmd_conv_wino44_workspace_floats(C.byref(a))
     outs = []
     for _ in range(2):

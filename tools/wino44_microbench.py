@@ -84,7 +84,7 @@ def main():
             out[k] = {"min_us": round(ts[0], 1), "median_us": round(ts[len(ts) // 2], 1),
                       "kernels_us": {r["kernel"]: round(r["ms"] * 1e3 / r["calls"], 1) for r in recs},
                       "kernels_sum_us": round(sum(r["ms"] * 1e3 / args.iters for r in recs), 1)}
-    a = ops._wino44_args(B, H, W, C1, up, C2, Cout, 3, "reflect", "elu", 0.0)
+    a = ops._conv_args(B, H, W, C1, up, C2, Cout, 3, "reflect", "elu", 0.0)
     l = _lib.lib()
     ntp = -(-out["tiles"] // 32) * 32
     k1, k2, co = -(-C1 // 32) * 32, -(-C2 // 32) * 32, -(-Cout // 32) * 32

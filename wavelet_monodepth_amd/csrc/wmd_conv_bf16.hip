@@ -287,20 +287,13 @@ struct Bf16Plan {
     size_t workspace_floats;
 };
 
-// the shape / feature rules of include/wmd.h; 0 or a negative status with the error text set
+// the operator's contract, then the family's own shape / feature rules of include/wmd.h (no tensor pointer is read: the
+// queries answer from this); 0 or a negative status with the error text set
 int bf16_rules(const wmd_conv_args* g, int terms, const char* who) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "%s: null args", who);
     if (terms != 1 && terms != 3) return fail(WMD_ERR_BAD_ARG, "%s: terms=%d (1 or 3)", who, terms);
-    if (!g->x1 || !g->wp || !g->y) return fail(WMD_ERR_BAD_ARG, "%s: null tensor pointer", who);
-    if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "%s: C2=%d but x2 is null", who, g->C2);
-    if (g->up1 != 1 && g->up1 != 2) return fail(WMD_ERR_BAD_ARG, "%s: up1=%d", who, g->up1);
-    if (g->pad_mode < 0 || g->pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "%s: pad_mode=%d", who, g->pad_mode);
-    if (g->act < 0 || g->act > 3) return fail(WMD_ERR_BAD_ARG, "%s: act=%d", who, g->act);
-    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->C1 <= 0 || g->C2 < 0 || g->Cout <= 0)
-        return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d C1=%d C2=%d Cout=%d", who, g->B, g->H, g->W, g->C1, g->C2, g->Cout);
-    if (g->up1 == 2 && ((g->H | g->W) & 1)) return fail(WMD_ERR_BAD_SHAPE, "%s: up1=2 needs even H,W", who);
-    if (g->ksize == 3 && g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "%s: reflect padding needs H,W >= 2 (got %dx%d)", who, g->H, g->W);
+    const int st = conv_check_problem(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, g->act, who);
+    if (st) return st;
     if (g->ksize != 3) return fail(WMD_ERR_UNSUPPORTED, "%s: ksize=%d (3x3 only)", who, g->ksize);
     if (g->pad_mode == WMD_PAD_REPLICATE) return fail(WMD_ERR_UNSUPPORTED, "%s: replicate padding", who);
     if (g->gate) return fail(WMD_ERR_UNSUPPORTED, "%s: gate is not implemented by the bf16 kernels", who);
@@ -398,6 +391,7 @@ extern "C" size_t wmd_conv_bf16_workspace_floats(const wmd_conv_args* g, int ter
 extern "C" int wmd_conv_bf16_fwd(const wmd_conv_args* g, int terms, void* stream) {
     const char* who = "wmd_conv_bf16_fwd";
     int st = bf16_rules(g, terms, who);
+    if (!st) st = conv_check_tensors(g, who);
     if (st) return st;
     Bf16Plan plan;
     const int forced = bf16_plan(g, &plan, who);

@@ -116,18 +116,6 @@ void launch_dgrad_fold(const float* g, float* dx1, float* dx2, int B, int C1, in
                        W, up1, pad_mode, halo, x1_fwd, x1_act, x1_slope);
 }
 
-int validate_bwd(int B, int H, int W, int C1, int up1, int C2, int Cout, int ksize, int pad_mode, const char* who) {
-    if (B <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || Cout <= 0)
-        return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d C1=%d C2=%d Cout=%d", who, B, H, W, C1, C2, Cout);
-    if (ksize != 1 && ksize != 3) return fail(WMD_ERR_UNSUPPORTED, "%s: ksize=%d", who, ksize);
-    if (up1 != 1 && up1 != 2) return fail(WMD_ERR_BAD_ARG, "%s: up1=%d", who, up1);
-    if (up1 == 2 && ((H | W) & 1)) return fail(WMD_ERR_BAD_SHAPE, "%s: up1=2 needs even H,W", who);
-    if (pad_mode < 0 || pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "%s: pad_mode=%d", who, pad_mode);
-    if (ksize == 3 && pad_mode == WMD_PAD_REFLECT && (H < 2 || W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "%s: reflect padding needs H,W >= 2", who);
-    return WMD_OK;
-}
-
 }  // namespace wmd
 
 using namespace wmd;
@@ -183,7 +171,7 @@ extern "C" int wmd_conv_dgrad(const wmd_conv_dgrad_args* g, void* stream) {
     if (!g->dz || !g->wp_dgrad) return fail(WMD_ERR_BAD_ARG, "wmd_conv_dgrad: null tensor pointer");
     if (!g->dx1 && !g->dx2) return WMD_OK;
     if (g->dx2 && g->C2 <= 0) return fail(WMD_ERR_BAD_ARG, "wmd_conv_dgrad: dx2 given but C2=%d", g->C2);
-    int st = validate_bwd(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, "wmd_conv_dgrad");
+    int st = conv_check_problem(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, WMD_ACT_NONE, "wmd_conv_dgrad");
     if (st) return st;
     if (g->ksize == 1 && g->up1 == 2) return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_dgrad: 1x1 with upsampled input");
     const int halo = g->ksize == 3 ? 1 : 0;

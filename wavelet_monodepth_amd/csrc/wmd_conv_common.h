@@ -428,9 +428,8 @@ struct WgradKArgs {
 template <int TH, int TW, int WCO, int WCI>
 void launch_wgrad_wino32(const WgradKArgs& a, dim3 grid, hipStream_t s);
 
-// wmd_conv_bwd.hip: the shape checks every backward entry point shares, and conv_dgrad_fold_kernel (the adjoint of pad + concat +
-// upsample on a padded-domain gradient g) as the data gradient and the depthwise backward launch it
-int validate_bwd(int B, int H, int W, int C1, int up1, int C2, int Cout, int ksize, int pad_mode, const char* who);
+// wmd_conv_bwd.hip: conv_dgrad_fold_kernel (the adjoint of pad + concat + upsample on a padded-domain gradient g) as the data gradient
+// and the depthwise backward launch it
 void launch_dgrad_fold(const float* g, float* dx1, float* dx2, int B, int C1, int C2, int H, int W, int up1, int pad_mode, int halo,
                        const float* x1_fwd, int x1_act, float x1_slope, hipStream_t s);
 

@@ -1151,27 +1151,25 @@ extern "C" int wmd_conv_list_tile_supported(int tile_h, int tile_w) {
     return 0;
 }
 
-static int validate_conv(const wmd_conv_args* g, const char* who) {
-    if (!g) return fail(WMD_ERR_BAD_ARG, "%s: null args", who);
+// The operator's contract (include/wmd.h, at wmd_conv_args): the shared rules in their documented order.  Reads no pointer.
+int wmd::conv_check_problem(int B, int H, int W, int C1, int up1, int C2, int Cout, int ksize, int pad_mode, int act, const char* who) {
+    if (B <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 < 0 || Cout <= 0)
+        return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d C1=%d C2=%d Cout=%d", who, B, H, W, C1, C2, Cout);
+    if (ksize != 1 && ksize != 3) return fail(WMD_ERR_UNSUPPORTED, "%s: ksize=%d", who, ksize);
+    if (up1 != 1 && up1 != 2) return fail(WMD_ERR_BAD_ARG, "%s: up1=%d", who, up1);
+    if (up1 == 2 && ((H | W) & 1)) return fail(WMD_ERR_BAD_SHAPE, "%s: up1=2 needs even H,W", who);
+    if (pad_mode < 0 || pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "%s: pad_mode=%d", who, pad_mode);
+    if (act < 0 || act > 3) return fail(WMD_ERR_BAD_ARG, "%s: act=%d", who, act);
+    // ReflectionPad2d(1) requires every padded dimension to be >= 2 (torch raises otherwise)
+    if (ksize == 3 && pad_mode == WMD_PAD_REFLECT && (H < 2 || W < 2))
+        return fail(WMD_ERR_BAD_SHAPE, "%s: reflect padding needs H,W >= 2 (got %dx%d)", who, H, W);
+    return WMD_OK;
+}
+
+// The tensors of a launch, after the problem check.
+int wmd::conv_check_tensors(const wmd_conv_args* g, const char* who) {
     if (!g->x1 || !g->wp || !g->y) return fail(WMD_ERR_BAD_ARG, "%s: null tensor pointer", who);
     if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "%s: C2=%d but x2 is null", who, g->C2);
-    if (g->B <= 0 || g->H <= 0 || g->W <= 0 || g->C1 <= 0 || g->C2 < 0 || g->Cout <= 0)
-        return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d C1=%d C2=%d Cout=%d", who, g->B, g->H, g->W, g->C1, g->C2,
-                    g->Cout);
-    if (g->ksize != 1 && g->ksize != 3) return fail(WMD_ERR_UNSUPPORTED, "%s: ksize=%d", who, g->ksize);
-    if (g->up1 != 1 && g->up1 != 2) return fail(WMD_ERR_BAD_ARG, "%s: up1=%d", who, g->up1);
-    if (g->up1 == 2 && ((g->H | g->W) & 1)) return fail(WMD_ERR_BAD_SHAPE, "%s: up1=2 needs even H,W", who);
-    if (g->pad_mode < 0 || g->pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "%s: pad_mode=%d", who, g->pad_mode);
-    if (g->act < 0 || g->act > 3) return fail(WMD_ERR_BAD_ARG, "%s: act=%d", who, g->act);
-    // ReflectionPad2d(1) requires every padded dimension to be >= 2 (torch raises otherwise)
-    if (g->ksize == 3 && g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "%s: reflect padding needs H,W >= 2 (got %dx%d)", who, g->H, g->W);
-    if (g->out_tiles) {   // work-list form
-        if (!g->out_tile_count || !g->out_mask || g->ksize != 3 || !g->wp_wino || g->gate)
-            return fail(WMD_ERR_BAD_ARG, "%s: a tile list needs its count, out_mask, a 3x3 layer with wp_wino and no gate", who);
-        if (!wmd_conv_list_tile_supported(g->out_tile_h, g->out_tile_w))
-            return fail(WMD_ERR_UNSUPPORTED, "%s: no work-list kernel for %dx%d tiles", who, g->out_tile_h, g->out_tile_w);
-    }
     return WMD_OK;
 }
 
@@ -1190,8 +1188,17 @@ extern "C" int wmd_conv_fwd_plan(const wmd_conv_args* g, int* ksplit) {
 }
 
 extern "C" int wmd_conv_fwd(const wmd_conv_args* g, void* stream) {
-    int st = validate_conv(g, "wmd_conv_fwd");
+    const char* who = "wmd_conv_fwd";
+    if (!g) return fail(WMD_ERR_BAD_ARG, "%s: null args", who);
+    int st = conv_check_problem(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, g->act, who);
+    if (!st) st = conv_check_tensors(g, who);
     if (st) return st;
+    if (g->out_tiles) {   // work-list form
+        if (!g->out_tile_count || !g->out_mask || g->ksize != 3 || !g->wp_wino || g->gate)
+            return fail(WMD_ERR_BAD_ARG, "%s: a tile list needs its count, out_mask, a 3x3 layer with wp_wino and no gate", who);
+        if (!wmd_conv_list_tile_supported(g->out_tile_h, g->out_tile_w))
+            return fail(WMD_ERR_UNSUPPORTED, "%s: no work-list kernel for %dx%d tiles", who, g->out_tile_h, g->out_tile_w);
+    }
     return run_conv(g, 0, g->H / g->up1, g->W / g->up1, stream);
 }
 

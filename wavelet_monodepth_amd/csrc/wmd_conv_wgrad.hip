@@ -861,7 +861,7 @@ extern "C" int wmd_conv_wgrad(const wmd_conv_wgrad_args* g, void* stream) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_conv_wgrad: null args");
     if (!g->x1 || !g->dz || !g->dw) return fail(WMD_ERR_BAD_ARG, "wmd_conv_wgrad: null tensor pointer");
     if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "wmd_conv_wgrad: C2=%d but x2 is null", g->C2);
-    int st = validate_bwd(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, "wmd_conv_wgrad");
+    int st = conv_check_problem(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, WMD_ACT_NONE, "wmd_conv_wgrad");
     if (st) return st;
     if (g->ksize == 1 && g->up1 == 2) return fail(WMD_ERR_UNSUPPORTED, "wmd_conv_wgrad: 1x1 with upsampled input");
     if (wgrad_forced_cfg_invalid(g))

@@ -401,18 +401,12 @@ W44Dims w44_dims(int B, int H, int W, int C1, int C2, int Cout) {
 
 constexpr size_t kMaxImageBytes = (size_t)1 << 31;   // 32-bit byte offsets inside every image
 
-// the problem alone -- shapes, modes, and which optional features are asked for (a mask, a gate, a tile list: by being
-// non-null); no tensor pointer is required: what wmd_conv_wino44_supported / _workspace_floats answer from
+// the problem alone -- the operator's contract, then which optional features are asked for (a mask, a gate, a tile list: by
+// being non-null) and the family's limits; no tensor pointer is required: what wmd_conv_wino44_supported / _workspace_floats answer from
 int w44_validate(const wmd_conv_args* g, const char* who) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "%s: null args", who);
-    if (g->up1 != 1 && g->up1 != 2) return fail(WMD_ERR_BAD_ARG, "%s: up1=%d", who, g->up1);
-    if (g->pad_mode < 0 || g->pad_mode > 2) return fail(WMD_ERR_BAD_ARG, "%s: pad_mode=%d", who, g->pad_mode);
-    if (g->act < 0 || g->act > 3) return fail(WMD_ERR_BAD_ARG, "%s: act=%d", who, g->act);
-    if (g->B < 1 || g->H < 1 || g->W < 1 || g->C1 < 1 || g->C2 < 0 || g->Cout < 1)
-        return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d C1=%d C2=%d Cout=%d", who, g->B, g->H, g->W, g->C1, g->C2, g->Cout);
-    if (g->up1 == 2 && ((g->H | g->W) & 1)) return fail(WMD_ERR_BAD_SHAPE, "%s: up1=2 needs even H,W", who);
-    if (g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "%s: reflect padding needs H,W >= 2 (got %dx%d)", who, g->H, g->W);
+    const int st = conv_check_problem(g->B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, g->act, who);
+    if (st) return st;
     if (g->ksize != 3) return fail(WMD_ERR_UNSUPPORTED, "%s: ksize=%d (3x3 only)", who, g->ksize);
     if (g->gate) return fail(WMD_ERR_UNSUPPORTED, "%s: gate is not implemented by the F(4x4,3x3) kernels", who);
     if (g->in_mask || g->out_mask || g->out_tiles || g->out_tile_count)
@@ -427,13 +421,6 @@ int w44_validate(const wmd_conv_args* g, const char* who) {
         (size_t)d.Ktot * d.NTp >= kMaxImageBytes / 4 || (size_t)g->B * g->Cout * hw * 4 >= kMaxImageBytes ||
         (size_t)g->B * std::max(g->C1, g->C2) * hw * 4 >= kMaxImageBytes)
         return fail(WMD_ERR_UNSUPPORTED, "%s: a tensor, the weight image or a workspace image exceeds 2 GiB", who);
-    return WMD_OK;
-}
-
-// the tensors of a launch
-int w44_validate_pointers(const wmd_conv_args* g, const char* who) {
-    if (!g->x1 || !g->wp || !g->y) return fail(WMD_ERR_BAD_ARG, "%s: null tensor pointer", who);
-    if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "%s: C2=%d but x2 is null", who, g->C2);
     return WMD_OK;
 }
 
@@ -470,7 +457,7 @@ extern "C" size_t wmd_conv_wino44_workspace_floats(const wmd_conv_args* g) {
 extern "C" int wmd_conv_wino44_fwd(const wmd_conv_args* g, void* stream) {
     const char* who = "wmd_conv_wino44_fwd";
     int rc = w44_validate(g, who);
-    if (rc == WMD_OK) rc = w44_validate_pointers(g, who);
+    if (rc == WMD_OK) rc = conv_check_tensors(g, who);
     if (rc != WMD_OK) return rc;
     const W44Dims d = w44_dims(g->B, g->H, g->W, g->C1, g->C2, g->Cout);
     if (!g->workspace || g->workspace_floats < d.v_floats + d.m_floats)

@@ -101,7 +101,7 @@ static int dw_check(const char* who, const wmd_dwconv_args* g) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "%s: null args", who);
     if (!g->x1 || !g->w) return fail(WMD_ERR_BAD_ARG, "%s: null tensor pointer", who);
     if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "%s: C2=%d but x2 is null", who, g->C2);
-    int st = validate_bwd(g->B, g->H, g->W, g->C1, g->up1, g->C2, 1, 3, g->pad_mode, who);
+    int st = conv_check_problem(g->B, g->H, g->W, g->C1, g->up1, g->C2, 1, 3, g->pad_mode, WMD_ACT_NONE, who);
     if (st) return st;
     if ((double)(g->C1 + g->C2) * g->B > 65535.0) return fail(WMD_ERR_UNSUPPORTED, "%s: B*C > 65535", who);
     if ((double)g->B * (g->C1 + g->C2) * (g->H + 2) * (g->W + 2) > 2147483647.0) return fail(WMD_ERR_UNSUPPORTED, "%s: more than 2^31 elements", who);

@@ -113,6 +113,12 @@ __device__ __forceinline__ unsigned order_key(float f) {
 }
 __device__ __forceinline__ float order_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
+// wmd_conv_fwd.hip: the fused convolution's contract (include/wmd.h, at wmd_conv_args), under the entry point's name `who`.  Every entry
+// that takes the problem calls conv_check_problem before its own rules (act: WMD_ACT_NONE where the entry has no activation); it reads no
+// pointer, so the shape queries answer from it alone.  conv_check_tensors: x1 / wp / y, and x2 when C2 > 0 -- the entries that launch.
+int conv_check_problem(int B, int H, int W, int C1, int up1, int C2, int Cout, int ksize, int pad_mode, int act, const char* who);
+int conv_check_tensors(const wmd_conv_args* g, const char* who);
+
 // The wavelet heads' front end.  Every WMD_HEAD* / WMD_SHIFTSUM* switch, read once per process (wmd_head.hip):
 struct HeadSwitches {
     bool chain;              // WMD_HEAD_CHAIN=0: the two-launch heads stay on the FUSE form of conv_fwd_kernel

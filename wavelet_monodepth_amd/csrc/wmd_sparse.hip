@@ -797,18 +797,13 @@ extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
     if (!g->x1 || !g->out_coords || !g->out_nnz || !g->wp || !g->y)
         return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: null pointer");
     if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: C2=%d but x2 is null", g->C2);
-    if (g->H <= 0 || g->W <= 0 || g->C1 <= 0 || g->C2 < 0 || g->Cout <= 0 || g->max_out < 0)
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: H=%d W=%d C1=%d C2=%d Cout=%d", g->H, g->W, g->C1, g->C2, g->Cout);
-    if (g->ksize != 1 && g->ksize != 3) return fail(WMD_ERR_UNSUPPORTED, "wmd_sparse_conv: ksize=%d", g->ksize);
-    if (g->up1 != 1 && g->up1 != 2) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: up1=%d", g->up1);
-    if (g->up1 == 2 && ((g->H | g->W) & 1))
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: a 2x-upsampled source needs even H, W (got %dx%d)", g->H, g->W);
-    if (g->ksize == 3 && g->pad_mode == WMD_PAD_REFLECT && (g->H < 2 || g->W < 2))
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: reflection padding needs H, W >= 2 (got %dx%d)", g->H, g->W);
+    const int B = g->B > 1 ? g->B : 1;
+    const int st = conv_check_problem(B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, g->act, "wmd_sparse_conv");
+    if (st) return st;
+    if (g->max_out < 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: max_out=%d", g->max_out);
     if (g->c1_off < 0 || g->c1_off + g->C1 > g->C1tot) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: channel slice");
     if (g->wp2 && (g->Cout > 16 || g->c1_off2 < 0 || g->c1_off2 + g->C1 > g->C1tot || g->C2 != 0))
         return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: dual-head mode needs Cout <= 16, C2 == 0 and a valid slice");
-    if (g->pad_mode < 0 || g->pad_mode > 2 || g->act < 0 || g->act > 3) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: enum");
     if (g->max_out == 0) return WMD_OK;
     SparseKArgs a;
     a.g = *g;
@@ -818,7 +813,6 @@ extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
     a.W1 = g->W / g->up1;
     a.plane = (size_t)g->H * g->W;
     a.plane1 = (size_t)(g->H / g->up1) * a.W1;
-    const int B = g->B > 1 ? g->B : 1;
     if (B > 65535) return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: B=%d", B);
     a.nnz_stride = B > 1 ? g->nnz_stride : 0;
     static const int split_waves = [] { const char* e = getenv("WMD_SPARSE_SPLIT_WAVES"); return e ? atoi(e) : 2048; }();

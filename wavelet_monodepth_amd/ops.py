@@ -230,6 +230,26 @@ def pack_weights_wino(weight, dgrad=False):
 # dense convolution
 # ---------------------------------------------------------------------------------------------
 
+def _conv_problem(x1, x2, up1, cout, cin=None):
+    """The problem (B, H, W, C1, up1, C2, cout) of upsample(x1) ++ x2 -> conv; raises for a skip tensor of another size and,
+    given the filter's input channels `cin`, for a channel mismatch."""
+    B, C1 = x1.shape[0], x1.shape[1]
+    H, W = x1.shape[2] * up1, x1.shape[3] * up1
+    C2 = 0 if x2 is None else x2.shape[1]
+    if cin is not None and cin != C1 + C2:
+        raise _lib.WmdError("weight expects %d input channels, got %d" % (cin, C1 + C2))
+    if x2 is not None and (x2.shape[0] != B or x2.shape[2] != H or x2.shape[3] != W):
+        raise _lib.WmdError("skip tensor %s does not match upsampled input %s" % (tuple(x2.shape), (B, C1, H, W)))
+    return B, H, W, C1, up1, C2, cout
+
+
+def _conv_args(B, H, W, C1, up1, C2, cout, ksize, pad, act, slope):
+    """wmd_conv_args of a problem without its tensors: what the shape queries read; a launch path sets its pointers."""
+    return _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad], act=ACT[act],
+                         slope=float(slope), x1=None, x2=None, wp=None, bias=None, y=None, workspace=None, workspace_floats=0,
+                         tune_cfg=0, tune_ksplit=0)
+
+
 def _conv_fwd_raw(x1, x2, wp, bias, cout, ksize, pad, act, slope, up1, wp_wino=None, in_mask=None, out_mask=None, out=None,
                   in_mask_2x2=False, out_tiles=None):
     """in_mask / out_mask (uint8 [B,H,W]) + out (zero-initialised [B,cout,H,W]): block-sparse execution, see
@@ -238,18 +258,13 @@ def _conv_fwd_raw(x1, x2, wp, bias, cout, ksize, pad, act, slope, up1, wp_wino=N
     sparse_ops.mask_level_lists) -- only listed tiles are computed, the split of the reduction is chosen on the device.
     """
     l = _lib.lib()
-    B, C1 = x1.shape[0], x1.shape[1]
-    H, W = x1.shape[2] * up1, x1.shape[3] * up1
-    C2 = 0 if x2 is None else x2.shape[1]
-    if x2 is not None and (x2.shape[0] != B or x2.shape[2] != H or x2.shape[3] != W):
-        raise _lib.WmdError("skip tensor %s does not match upsampled input %s" % (tuple(x2.shape), (B, C1, H, W)))
+    B, H, W, C1, up1, C2, cout = _conv_problem(x1, x2, up1, cout)
     if out_mask is not None and out is None:
         raise _lib.WmdError("block-sparse convolution writes the active tiles only: pass a zero-initialised `out`")
     y = out if out is not None else torch.empty((B, cout, H, W), device=x1.device, dtype=torch.float32)
-    a = _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad], act=ACT[act],
-                      slope=float(slope), x1=ptr(x1), x2=ptr(x2), wp=ptr(wp), bias=ptr(bias), y=ptr(y),
-                      workspace=None, workspace_floats=0, tune_cfg=0, tune_ksplit=0, wp_wino=ptr(wp_wino),
-                      in_mask=ptr(in_mask), out_mask=ptr(out_mask), in_mask_2x2=int(bool(in_mask_2x2)))
+    a = _conv_args(B, H, W, C1, up1, C2, cout, ksize, pad, act, slope)
+    a.x1, a.x2, a.wp, a.bias, a.y, a.wp_wino = ptr(x1), ptr(x2), ptr(wp), ptr(bias), ptr(y), ptr(wp_wino)
+    a.in_mask, a.out_mask, a.in_mask_2x2 = ptr(in_mask), ptr(out_mask), int(bool(in_mask_2x2))
     if out_tiles is not None:
         tl, tc, th, tw = out_tiles
         a.out_tiles, a.out_tile_count, a.out_tile_h, a.out_tile_w = ptr(tl), ptr(tc), int(th), int(tw)
@@ -455,11 +470,8 @@ def conv2d_fused(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none
     so its backward takes the incoming gradient as dz (no wmd_act_bwd pass).  The derivative is linear, so gating each
     consumer's contribution before autograd sums them equals gating the sum."""
     _require_gpu(x1, x2, weight, bias)
-    ksize = weight.shape[-1]
-    cin = x1.shape[1] + (0 if x2 is None else x2.shape[1])
-    if weight.shape[1] != cin:
-        raise _lib.WmdError("weight expects %d input channels, got %d" % (weight.shape[1], cin))
-    return _ConvFn.apply(x1, x2, weight, bias, ksize, pad, act, slope, up1, x1_gate, grad_is_dz)
+    _conv_problem(x1, x2, up1, weight.shape[0], weight.shape[1])
+    return _ConvFn.apply(x1, x2, weight, bias, weight.shape[-1], pad, act, slope, up1, x1_gate, grad_is_dz)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -488,39 +500,23 @@ def pack_weights_bf16(weight, terms):
 
 def conv3x3_bf16_supported(B, H, W, C1, up1, C2, cout, pad="reflect", terms=3):
     """Does wmd_conv_bf16_fwd take this problem?  Shapes only, no GPU call (the decoders ask per trunk layer)."""
-    a = _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=3, pad_mode=PAD[pad], act=0, slope=0.0,
-                      x1=1, x2=1 if C2 else None, wp=1, bias=None, y=1, workspace=None, workspace_floats=0)
-    return bool(_lib.lib().wmd_conv_bf16_supported(C.byref(a), terms))
+    return bool(_lib.lib().wmd_conv_bf16_supported(C.byref(_conv_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0)), terms))
 
 
 def conv3x3_bf16_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none", slope=0.0, terms=3):
     """act( conv3x3( pad( cat[ nearest_up(x1, up1), x2 ] ) ) + bias ) with both operands rounded to bf16 (terms = 1) or split
     into bf16 head + tail, three products (terms = 3), fp32 accumulate -- the contract in include/wmd.h.  fp32 tensors in and
     out.  Inference operator; a problem the kernel does not take raises (it is never computed in fp32 instead)."""
-    _require_gpu(x1, x2, weight, bias)
-    if torch.is_grad_enabled() and (x1.requires_grad or weight.requires_grad or (x2 is not None and x2.requires_grad)
-                                    or (bias is not None and bias.requires_grad)):
-        raise _lib.WmdError("conv3x3_bf16_nograd is an inference operator (use conv2d_fused to train)")
+    x1, x2, bias, (B, H, W, C1, up1, C2, cout) = _nograd_operands("conv3x3_bf16_nograd", x1, weight, bias, x2, up1)
     if terms not in (1, 3):
         raise _lib.WmdError("terms must be 1 or 3, got %r" % (terms,))
     l = _lib.lib()
-    x1, x2, bias = _c(x1), _c(x2), _c(bias)
-    B, C1 = x1.shape[0], x1.shape[1]
-    H, W = x1.shape[2] * up1, x1.shape[3] * up1
-    C2 = 0 if x2 is None else x2.shape[1]
-    cout = weight.shape[0]
-    if weight.shape[1] != C1 + C2:
-        raise _lib.WmdError("weight expects %d input channels, got %d" % (weight.shape[1], C1 + C2))
-    if x2 is not None and (x2.shape[0] != B or x2.shape[2] != H or x2.shape[3] != W):
-        raise _lib.WmdError("skip tensor %s does not match upsampled input %s" % (tuple(x2.shape), (B, C1, H, W)))
-    a = _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=weight.shape[-1], pad_mode=PAD[pad], act=ACT[act],
-                      slope=float(slope), x1=ptr(x1), x2=ptr(x2), wp=1, bias=ptr(bias), y=1, workspace=None,
-                      workspace_floats=0, tune_cfg=0, tune_ksplit=0)
+    a = _conv_args(B, H, W, C1, up1, C2, cout, weight.shape[-1], pad, act, slope)
     if not l.wmd_conv_bf16_supported(C.byref(a), terms):
         raise _lib.WmdError("wmd_conv_bf16_fwd does not take this problem: %s" % l.wmd_last_error().decode())
     wp = pack_weights_bf16(weight, terms)
     y = torch.empty((B, cout, H, W), device=x1.device, dtype=torch.float32)
-    a.wp, a.y = ptr(wp), ptr(y)
+    a.x1, a.x2, a.wp, a.bias, a.y = ptr(x1), ptr(x2), ptr(wp), ptr(bias), ptr(y)
 
     def launch(choice):
         a.tune_cfg, a.tune_ksplit = choice
@@ -565,15 +561,9 @@ def pack_weights_wino44(weight, C1, up1):
     return _memo(weight, "_wmd_pack_w44_%d_%d" % (C1, up1), _pack_tag(weight), build)[0]
 
 
-def _wino44_args(B, H, W, C1, up1, C2, cout, ksize, pad, act, slope):
-    return _lib.ConvArgs(B=B, H=H, W=W, C1=C1, up1=up1, C2=C2, Cout=cout, ksize=ksize, pad_mode=PAD[pad], act=ACT[act],
-                         slope=float(slope), x1=None, x2=None, wp=None, bias=None, y=None, workspace=None, workspace_floats=0,
-                         tune_cfg=0, tune_ksplit=0)
-
-
 def conv3x3_wino44_supported(B, H, W, C1, up1, C2, cout, pad="reflect"):
     """Does wmd_conv_wino44_fwd take this problem?  Shapes only, no GPU call."""
-    return bool(_lib.lib().wmd_conv_wino44_supported(C.byref(_wino44_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0))))
+    return bool(_lib.lib().wmd_conv_wino44_supported(C.byref(_conv_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0))))
 
 
 def wino44_offered(B, H, W, C1, up1, C2, cout, pad="reflect"):
@@ -581,7 +571,7 @@ def wino44_offered(B, H, W, C1, up1, C2, cout, pad="reflect"):
     of at most WINO44_MAX_WORKSPACE_FLOATS."""
     if not _WINO44 or B * ((H + 3) // 4) * ((W + 3) // 4) < WINO44_MIN_TILES:
         return False
-    a = _wino44_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0)
+    a = _conv_args(B, H, W, C1, up1, C2, cout, 3, pad, "none", 0.0)
     n = _lib.lib().wmd_conv_wino44_workspace_floats(C.byref(a))
     return 0 < n <= WINO44_MAX_WORKSPACE_FLOATS
 
@@ -591,15 +581,7 @@ def _nograd_operands(name, x1, weight, bias, x2, up1):
     if torch.is_grad_enabled() and (x1.requires_grad or weight.requires_grad or (x2 is not None and x2.requires_grad)
                                     or (bias is not None and bias.requires_grad)):
         raise _lib.WmdError("%s is an inference operator (use conv2d_fused to train)" % name)
-    x1, x2, bias = _c(x1), _c(x2), _c(bias)
-    B, C1 = x1.shape[0], x1.shape[1]
-    H, W = x1.shape[2] * up1, x1.shape[3] * up1
-    C2 = 0 if x2 is None else x2.shape[1]
-    if weight.shape[1] != C1 + C2:
-        raise _lib.WmdError("weight expects %d input channels, got %d" % (weight.shape[1], C1 + C2))
-    if x2 is not None and (x2.shape[0] != B or x2.shape[2] != H or x2.shape[3] != W):
-        raise _lib.WmdError("skip tensor %s does not match upsampled input %s" % (tuple(x2.shape), (B, C1, H, W)))
-    return x1, x2, bias, (B, H, W, C1, up1, C2, weight.shape[0])
+    return _c(x1), _c(x2), _c(bias), _conv_problem(x1, x2, up1, weight.shape[0], weight.shape[1])
 
 
 def conv3x3_wino44_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", act="none", slope=0.0):
@@ -608,7 +590,7 @@ def conv3x3_wino44_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", 
     raises (it is never computed on another path instead)."""
     x1, x2, bias, (B, H, W, C1, up1, C2, cout) = _nograd_operands("conv3x3_wino44_nograd", x1, weight, bias, x2, up1)
     l = _lib.lib()
-    a = _wino44_args(B, H, W, C1, up1, C2, cout, weight.shape[-1], pad, act, slope)
+    a = _conv_args(B, H, W, C1, up1, C2, cout, weight.shape[-1], pad, act, slope)
     if not l.wmd_conv_wino44_supported(C.byref(a)):
         raise _lib.WmdError("wmd_conv_wino44_fwd does not take this problem: %s" % l.wmd_last_error().decode())
     wp = pack_weights_wino44(weight, C1, up1)
@@ -633,10 +615,7 @@ def conv3x3_routed_nograd(x1, weight, bias=None, x2=None, up1=1, pad="reflect", 
 
     if not _WINO44 or weight.shape[-1] != 3 or x1.dim() != 4:
         return fused()
-    B, C1 = x1.shape[0], x1.shape[1]
-    H, W = x1.shape[2] * up1, x1.shape[3] * up1
-    C2 = 0 if x2 is None else x2.shape[1]
-    cout = weight.shape[0]
+    B, H, W, C1, up1, C2, cout = _conv_problem(x1, x2, up1, weight.shape[0], weight.shape[1])
     key = "route|conv|%d|%d|%d|%d|%d|%d|%d|3" % (B, H, W, C1, up1, C2, cout)
     use = _wino44_route.get(key)
     if use is None:
