@@ -517,7 +517,10 @@ int wmd_head_level_pyramid_fwd(const wmd_head_level_args* args, const wmd_head_s
  * [B,n_out,H,W] (rows [LL], +, -) and the LeakyReLU outputs mid [B,Ct,H,W] of the stacked 1x1 stage:
  *   dzmid = act'(mid) * conv3x3^T(dy3)  (the 1x1 stage's pre-activation gradient),  dw3 / db3 per head.
  * One pass each over mid for the data and the weight gradient, no padded-domain buffer (wmd_head_bwd.hip).  At most 24
- * 64-channel slices over all heads (WMD_ERR_UNSUPPORTED beyond: use wmd_conv_dgrad / wmd_conv_wgrad on the stacked filter). */
+ * 64-channel slices over all heads (WMD_ERR_UNSUPPORTED beyond: use wmd_conv_dgrad / wmd_conv_wgrad on the stacked filter).
+ * Alignment: when H*W is a multiple of 4 the planes of mid and dzmid are read and written sixteen bytes at a time, so both
+ * pointers must be 16-byte aligned (any float pointer otherwise); the workspace always.  WMD_ERR_BAD_ARG if not: the last refusal
+ * before a launch, after the workspace's size (the query answers for any pointers).                                         */
 typedef struct {
     int row0;          /* first plane of dy3 that belongs to this head                   */
     int nrows;         /* its output channels: 3 (high-frequency heads) or 1 (low-pass)  */
@@ -548,7 +551,9 @@ int wmd_head3x3_bwd(const wmd_head3x3_bwd_args* args, void* stream);
 /* Backward of the 1x1 stage of a level's wavelet heads (training): the first layers Conv1x1(C, C | C/4) of every head of a
  * level, stacked along the output channels (depth_decoder.py:104-136), given the pre-activation gradient dz [B,Ct,H,W] of the
  * stack (wmd_head3x3_bwd's dzmid):  dx = act_x'(x) * w1^T dz (optional),  dw1 = sum_p dz (x) x,  db1 = sum_p dz.
- * One pass over dz and x each for the data and the weight gradient (wmd_head_bwd1.hip).                                   */
+ * One pass over dz and x each for the data and the weight gradient (wmd_head_bwd1.hip).
+ * Alignment: when H*W is a multiple of 4, dz, x and dx (if given) must be 16-byte aligned (16-byte loads and stores of their
+ * planes); the workspace always.  WMD_ERR_BAD_ARG if not: the last refusal before a launch, after the workspace's size.      */
 typedef struct {
     int B, H, W;
     int C;             /* channels of x                                                  */

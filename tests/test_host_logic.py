@@ -346,6 +346,54 @@ def test_round3_entry_points_validate_arguments_without_gpu():
     assert lib.wmd_head_bwd(C.byref(a3), C.byref(a1), None) == -3                                  # the merged form: 3-channel heads only
 
 
+def test_head_backward_refuses_misaligned_pointers_without_gpu():
+    """Planes of a multiple of four pixels move sixteen bytes at a time: wmd_head3x3_bwd / wmd_head1x1_bwd / wmd_head_bwd refuse
+    mid, dzmid, dz, x, dx that are not 16-byte aligned then, and a misaligned workspace always, with WMD_ERR_BAD_ARG (-1) -- the last
+    refusal before a launch, after the workspace's size (-5), so the queries answer for any pointers.  Nothing is launched."""
+    import ctypes as C
+    from wavelet_monodepth_amd import _lib
+    lib = _lib.lib()
+    BIG = 1 << 40       # stand-in workspaces large enough for every shape below
+    a3 = _lib.Head3x3BwdArgs(B=1, H=8, W=8, Ct=64, n_out=6, pad_mode=1, act=2, slope=0.1, dy3=4, mid=0x20, dzmid=0x10, n_heads=1,
+                             workspace=0x1000, workspace_floats=BIG)
+    a3.head[0] = _lib.HeadBwdHead(row0=0, nrows=3, ch0=0, nch=32, w3=4, dw3=4, db3=4)
+    a1 = _lib.Head1x1BwdArgs(B=1, H=8, W=8, C=32, Ct=64, x_act=1, x_slope=0.0, dz=0x10, x=0x30, w1=4, dx=0x40, dw1=4, db1=4,
+                             workspace=0x2000, workspace_floats=BIG)
+
+    def refused(fn, *args):
+        return fn(*[C.byref(a) for a in args], None) == -1 and b"16-byte aligned" in lib.wmd_last_error()
+    for field, aligned in (("mid", 0x20), ("dzmid", 0x10)):
+        for off in (4, 8, 12):
+            setattr(a3, field, aligned + off)
+            for H, W in ((8, 8), (8, 7), (8, 5), (2, 2)):                                            # 64, 56, 40 and 4 pixels
+                a3.H, a3.W = H, W
+                assert refused(lib.wmd_head3x3_bwd, a3), (field, off, H, W)
+                assert lib.wmd_head3x3_bwd_workspace_floats(C.byref(a3)) > 0                         # the query has no workspace to judge
+            a3.workspace_floats = 0
+            assert lib.wmd_head3x3_bwd(C.byref(a3), None) == -5                                      # the workspace's size comes first
+            a3.workspace_floats, a3.H, a3.W = BIG, 8, 8
+        setattr(a3, field, aligned)
+    a3.workspace = 0x1004
+    assert refused(lib.wmd_head3x3_bwd, a3) and b"workspace" in lib.wmd_last_error()
+    a3.H, a3.W = 7, 5                                                                                # the block partials are 16-byte stores on any plane
+    assert refused(lib.wmd_head3x3_bwd, a3) and b"workspace" in lib.wmd_last_error()
+    a3.workspace, a3.H, a3.W = 0x1000, 8, 8
+    for field, aligned in (("dz", 0x10), ("x", 0x30), ("dx", 0x40)):
+        for off in (4, 8, 12):
+            setattr(a1, field, aligned + off)
+            assert refused(lib.wmd_head1x1_bwd, a1) and b"wmd_head1x1_bwd" in lib.wmd_last_error(), (field, off)
+            assert lib.wmd_head1x1_bwd_workspace_floats(C.byref(a1)) > 0
+        if field != "dz":                                                                            # (a dz that is not a3's dzmid is refused as such)
+            assert refused(lib.wmd_head_bwd, a3, a1) and b"wmd_head1x1_bwd" in lib.wmd_last_error(), field
+        setattr(a1, field, aligned)
+    a3.mid = 0x24
+    assert refused(lib.wmd_head_bwd, a3, a1) and b"wmd_head3x3_bwd" in lib.wmd_last_error()
+    a3.mid = 0x20
+    a1.workspace = 0x2008
+    assert refused(lib.wmd_head1x1_bwd, a1) and b"workspace" in lib.wmd_last_error()
+    assert refused(lib.wmd_head_bwd, a3, a1) and b"workspace" in lib.wmd_last_error()
+
+
 # ---- NYUv2 Model(opts) (NYUv2/model.py:12-71) ------------------------------------------------------------------------------
 def test_nyu_model_picks_encoder_and_decoder_like_the_reference():
     from types import SimpleNamespace as NS

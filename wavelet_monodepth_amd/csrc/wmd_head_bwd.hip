@@ -912,6 +912,15 @@ static int head_bwd_validate(const wmd_head3x3_bwd_args* g, int* n_slices) {
     return WMD_OK;
 }
 
+// The last refusal before a launch (after the workspace size: a query, which has no workspace yet, answers for any pointers):
+// planes of a multiple of four pixels are read and written sixteen bytes at a time; the block partials always are
+static int head_bwd_aligned(const wmd_head3x3_bwd_args* g) {
+    if (((long)g->H * g->W) % 4 == 0 && (((uintptr_t)g->mid | (uintptr_t)g->dzmid) & 15) != 0)
+        return fail(WMD_ERR_BAD_ARG, "wmd_head3x3_bwd: mid and dzmid must be 16-byte aligned when H*W is a multiple of 4");
+    if (((uintptr_t)g->workspace & 15) != 0) return fail(WMD_ERR_BAD_ARG, "wmd_head3x3_bwd: the workspace must be 16-byte aligned");
+    return WMD_OK;
+}
+
 // may both stages run as head_bwd_fused32_kernel?  (two 3-channel heads of 32 channels each over a 32-channel x, whole 64-pixel
 // tiles, rows that are multiples of four pixels; WMD_HEAD_BWD_FUSED=0: never)
 static bool head_bwd_fused_ok(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_bwd_args* a1) {
@@ -1012,6 +1021,7 @@ extern "C" int wmd_head3x3_bwd(const wmd_head3x3_bwd_args* g, void* stream) {
     // (the 3x3-only size, smaller than the query's answer where the 1x1 stage would run more blocks)
     if (!g->workspace || g->workspace_floats < p.need3)
         return fail(WMD_ERR_WORKSPACE, "wmd_head3x3_bwd: workspace %zu < %zu floats", g->workspace_floats, p.need3);
+    if (int st = head_bwd_aligned(g)) return st;
     hipStream_t s = (hipStream_t)stream;
     float* ws = g->workspace;
     for (int nrows = 3; nrows >= 1; nrows -= 2) {   // one launch set per head kind: 3-row (+/-) heads, then the 1-row low-pass head
@@ -1043,6 +1053,8 @@ extern "C" int wmd_head_bwd(const wmd_head3x3_bwd_args* a3, const wmd_head1x1_bw
         return fail(WMD_ERR_WORKSPACE, "wmd_head_bwd: 3x3 workspace %zu < %zu floats", a3->workspace_floats, p.need3);
     if (!a1->workspace || a1->workspace_floats < p.need1)
         return fail(WMD_ERR_WORKSPACE, "wmd_head_bwd: 1x1 workspace %zu < %zu floats", a1->workspace_floats, p.need1);
+    if (int st = head_bwd_aligned(a3)) return st;
+    if (int st = head1x1_aligned(a1)) return st;
     const double ch = head_bwd_fill(a3, 3, p.nblk, a3->workspace, &m.h3);
     hipStream_t s = (hipStream_t)stream;
     m.n3 = m.h3.n_slices, m.n1d = a1->dx ? m.h1.n_igrp : 0, m.n1w = m.h1.n_cgrp * m.h1.n_igrp;

@@ -56,6 +56,7 @@ struct Head1x1K {
 // wmd_head_bwd1.hip, for wmd_head_bwd too: the argument checks of the 1x1 stage; its kernel arguments -> the floats of block
 // partials its workspace must hold
 int head1x1_validate(const wmd_head1x1_bwd_args* g);
+int head1x1_aligned(const wmd_head1x1_bwd_args* g);    // the alignment of dz, x, dx and the workspace: checked after the workspace size
 size_t head1x1_fill(const wmd_head1x1_bwd_args* g, Head1x1K* a);
 
 // ---- data gradient: D[pixel 16][ci 16] += A[pixel][c] * B[c][ci], A = dz, B = W1 ------------------------------------------

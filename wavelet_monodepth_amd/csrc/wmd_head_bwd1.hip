@@ -10,6 +10,7 @@
 // traffic time (110 + 79 us at the finest level of BASELINE config 2).  Here: fp32 16x16x4 MFMA straight from global memory,
 // pixels as the MFMA rows of the data gradient (a lane ends with 4 consecutive pixels of one channel: 16-byte gate loads /
 // stores) and as the reduction index of the weight gradient (16-byte loads of 16 consecutive pixels per lane for both operands).
+#include <cstdint>
 #include "wmd_head_bwd1.h"
 
 namespace wmd {
@@ -31,6 +32,15 @@ int head1x1_validate(const wmd_head1x1_bwd_args* g) {
     if (g->Ct % 8) return fail(WMD_ERR_UNSUPPORTED, "wmd_head1x1_bwd: Ct=%d is not a multiple of 8", g->Ct);
     if (g->x_act != WMD_ACT_NONE && g->x_act != WMD_ACT_LEAKY && g->x_act != WMD_ACT_ELU)
         return fail(WMD_ERR_UNSUPPORTED, "wmd_head1x1_bwd: x_act=%d (none, LeakyReLU or ELU)", g->x_act);
+    return WMD_OK;
+}
+
+// the last refusal before a launch (after the workspace size): planes of a multiple of four pixels are read and written sixteen
+// bytes at a time; the block partials always are
+int head1x1_aligned(const wmd_head1x1_bwd_args* g) {
+    if (((long)g->H * g->W) % 4 == 0 && (((uintptr_t)g->dz | (uintptr_t)g->x | (uintptr_t)g->dx) & 15) != 0)
+        return fail(WMD_ERR_BAD_ARG, "wmd_head1x1_bwd: dz, x and dx must be 16-byte aligned when H*W is a multiple of 4");
+    if (((uintptr_t)g->workspace & 15) != 0) return fail(WMD_ERR_BAD_ARG, "wmd_head1x1_bwd: the workspace must be 16-byte aligned");
     return WMD_OK;
 }
 
@@ -63,6 +73,7 @@ extern "C" int wmd_head1x1_bwd(const wmd_head1x1_bwd_args* g, void* stream) {
     const size_t need = head1x1_fill(g, &a);
     if (!g->workspace || g->workspace_floats < need)
         return fail(WMD_ERR_WORKSPACE, "wmd_head1x1_bwd: workspace %zu < %zu floats", g->workspace_floats, need);
+    if (int st = head1x1_aligned(g)) return st;
     hipStream_t s = (hipStream_t)stream;
     const double pix = (double)g->B * g->H * g->W;
     if (g->dx) {
