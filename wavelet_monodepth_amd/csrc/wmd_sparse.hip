@@ -821,11 +821,15 @@ extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int tiles = (g->max_out + 15) / 16;
     const int taps = g->ksize == 3 ? 9 : 1;
-    char pname[96] = "sparse_conv_kernel";
-    if (g_prof_on && getenv("WMD_SPARSE_PROF_SHAPES"))   // development: one profile line per layer shape
-        snprintf(pname, sizeof(pname), "sparse_conv_kernel C%d+%d->%d k%d %dx%d%s", g->C1, g->C2, g->Cout, g->ksize, g->H, g->W,
-                 g->wp2 ? " dual" : "");
-    ProfScope prof(pname, 0.0, 0.0, s);
+    // the profile record carries the template arguments of the instantiation that ran (the launch macro below spells them);
+    // WMD_SPARSE_PROF_SHAPES (development) appends the layer shape: one profile line per shape
+    char pname[160];
+    const bool prof_shapes = g_prof_on && getenv("WMD_SPARSE_PROF_SHAPES");
+    auto prof_name = [&](const char* inst) -> const char* {
+        if (!prof_shapes) return inst;
+        snprintf(pname, sizeof(pname), "%s C%d+%d->%d k%d %dx%d%s", inst, g->C1, g->C2, g->Cout, g->ksize, g->H, g->W, g->wp2 ? " dual" : "");
+        return pname;
+    };
     // MR out-channel tiles per block: as few as keeps the grid near the machine size -- a sparse launch has far fewer
     // pixel tiles than the GPU has SIMDs, so out-channel tiles go to separate blocks (each re-gathers the same few
     // pixels out of L2) until the capacity grid reaches ~512 blocks (measured: tools/sparse_microbench.py); a full-density fine level keeps MR large and
@@ -838,9 +842,12 @@ extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
     // itself); WMD_SPARSE_GRID overrides the total block target (development)
     static const int grid_target = [] { const char* e = getenv("WMD_SPARSE_GRID"); return e ? atoi(e) : 2048; }();
 #define WMD_SPARSE_LAUNCH(MR_, TAPS_, DUAL_, WK_, UN_, ROWS_)                                                          \
-    hipLaunchKernelGGL((sparse_conv_kernel<MR_, TAPS_, DUAL_, WK_, UN_, ROWS_>),                                       \
-                       dim3(std::max(1, std::min(tiles, grid_target / (((a.ncot + MR_ - 1) / MR_) * B))), (a.ncot + MR_ - 1) / MR_, B), \
-                       dim3(64 * WK_), 0, s, a)
+    do {                                                                                                               \
+        ProfScope prof(prof_name("sparse_conv_kernel<" #MR_ "," #TAPS_ "," #DUAL_ "," #WK_ "," #UN_ "," #ROWS_ ">"), 0.0, 0.0, s); \
+        hipLaunchKernelGGL((sparse_conv_kernel<MR_, TAPS_, DUAL_, WK_, UN_, ROWS_>),                                   \
+                           dim3(std::max(1, std::min(tiles, grid_target / (((a.ncot + MR_ - 1) / MR_) * B))), (a.ncot + MR_ - 1) / MR_, B), \
+                           dim3(64 * WK_), 0, s, a);                                                                   \
+    } while (0)
     static const int rows_off = [] { const char* e = getenv("WMD_SPARSE_ROWS"); return e && atoi(e) == 0; }();
     if (taps == 9 && g->W >= 3 && a.W1 >= 3 && !rows_off) {
         if (g->wp2) WMD_SPARSE_LAUNCH(1, 9, true, 8, 2, true);
