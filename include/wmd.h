@@ -1086,6 +1086,43 @@ int wmd_pose_head_bwd(const float* params, const float* means, const float* w, c
                       float* dx, float* dw, float* dbias, float* workspace, int B, int C, int H, int W, int F, int invert_mask,
                       float scale, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * Semi-global stereo matching: the candidates of depth-hint fusion
+ * ------------------------------------------------------------------ */
+
+/* The matcher of KITTI/precompute_depth_hints.py:42-63,127-151 (StereoSGBM there).  The contract is the integer specification
+ * in DESIGN.md ("Semi-global stereo matching"), which follows StereoSGBM's documented parameters and stages; the result
+ * equals tests/stereo_ref.py bit for bit and has NOT been compared with OpenCV's.
+ *   left, right uint8 [B,H,W,C], C = 1 or 3 (left = the image the map belongs to).  reverse: NULL or B bytes on the device;
+ *   image b is mirrored horizontally (both views) before matching and its map mirrored back when reverse[b] != 0.
+ *   disp int16 [B,H,W]: 16 x the pixel disparity, (min_disp - 1) * 16 where there is none (always left of column
+ *   min_disp + num_disp; right of W - 1 - that with reverse).
+ *   cost_out / S_out: NULL or uint16 [B,H,Wv,num_disp], Wv = W - min_disp - num_disp: the block costs and the summed
+ *   path costs over the valid rectangle, disparity innermost.
+ *   block = blockSize (the window is 2 (block / 2) + 1 wide), cap = preFilterCap, uniq = uniquenessRatio, disp12 =
+ *   disp12MaxDiff (<= 0 means 1), directions 5 or 8; speckle_win == 0 skips the speckle stage.
+ * workspace: wmd_stereo_sgbm_workspace_bytes(...) bytes, 256-byte aligned, at most about 1 GiB: images that do not fit
+ * run in several groups inside the call.  The query returns 0 for arguments the entry refuses.
+ * Refused before any HIP call: a NULL left / right / disp / workspace, C not 1 or 3, min_disp < 0, num_disp not a multiple
+ * of 16 in 16..256, block < 1, P1 < 0 or P1 > P2, directions not 5 or 8, uniq outside 0..100, a negative cap or speckle
+ * setting (WMD_ERR_BAD_ARG); a size < 1 or W <= min_disp + num_disp (WMD_ERR_BAD_SHAPE); a short or misaligned workspace
+ * (WMD_ERR_WORKSPACE); cap > 127, directions * (win^2 C (2 cap + 63) + P2) > 65535 (S would not fit 16 bits), a window
+ * that does not fit the LDS tile, a size above 65535 or more than 2^31 elements (WMD_ERR_UNSUPPORTED).
+ * 5 + directions launches and one memset per group, four more with the speckle stage.                                   */
+size_t wmd_stereo_sgbm_workspace_bytes(int B, int H, int W, int C, int min_disp, int num_disp, int block);
+int wmd_stereo_sgbm(const unsigned char* left, const unsigned char* right, const unsigned char* reverse, short* disp,
+                    unsigned short* cost_out, unsigned short* S_out, int B, int H, int W, int C, int min_disp, int num_disp,
+                    int block, int P1, int P2, int cap, int uniq, int speckle_win, int speckle_range, int disp12,
+                    int directions, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The speckle stage on its own, in place on disp int16 [B,H,W]: every 4-connected component -- neighbours both different
+ * from `invalid` and at most max_diff apart; a chain of such steps is one component whatever its ends differ by -- of at
+ * most max_size pixels becomes `invalid`.  Union-find over the whole map: a component may cross anything.  workspace:
+ * wmd_stereo_filter_speckles_workspace_bytes(B, H, W) bytes (0 for a bad shape).  Four launches.                         */
+size_t wmd_stereo_filter_speckles_workspace_bytes(int B, int H, int W);
+int wmd_stereo_filter_speckles(short* disp, int B, int H, int W, int invalid, int max_size, int max_diff, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

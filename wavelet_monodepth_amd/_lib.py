@@ -243,7 +243,11 @@ SIGNATURES = {
     "wmd_depth_hints_workspace_floats": (C.c_size_t, [C.c_int] * 4),
     "wmd_depth_hints_fuse": (C.c_int, [C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float] * 3 +
                              [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "wmd_lidar_depth_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "wmd_stereo_sgbm_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "wmd_stereo_sgbm": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 15 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wmd_stereo_filter_speckles_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "wmd_stereo_filter_speckles": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wmd_lidar_depth_workspace_bytes":(C.c_size_t, [C.c_int] * 3),
     "wmd_lidar_depth_maps": (C.c_int, [C.c_void_p] * 3 + [C.c_size_t] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wmd_lanczos_ksize": (C.c_int, [C.c_int] * 2),
     "wmd_lanczos_table": (C.c_int, [C.c_int] * 2 + [C.c_void_p] * 2 + [C.c_int]),

@@ -2,8 +2,8 @@
 // of one stereo pair -> per pixel the depth of the candidate whose reprojection of the other view matches the base image best
 // (0.85 SSIM + 0.15 L1, the trainer's compute_reprojection_loss).  The reference expands both images M-fold and runs
 // BackprojectDepth, Project3D, grid_sample, SSIM, argmin and gather; here it is one launch that reads every candidate plane
-// and the base image once and writes two planes (plus the M loss planes on request).  The stereo matcher that produces the
-// candidates is the caller's.
+// and the base image once and writes two planes (plus the M loss planes on request).  The candidates are the caller's, from
+// any matcher; wmd_stereo.hip is the library's.
 //
 // hints_fuse_kernel: a block of 256 threads (4 wavefronts) owns a 64 x 8 output tile; wavefront q owns rows 2q and 2q + 1,
 // lane x column x.  Per candidate the block warps the tile plus its one-pixel ReflectionPad2d ring (66 x 10 positions, each

@@ -5,8 +5,9 @@
                                                           of the other stereo view has the smallest 0.85 SSIM + 0.15 L1
     depth_hint_inputs(best_depth)                         datasets/mono_dataset.py:264-265 -- what the trainer's loss reads
 
-The stereo matcher that produces the candidates (OpenCV SGBM in the reference, twelve settings) is out of scope: the
-candidates come from the caller, from any matcher.  One HIP launch, no autograd, no CPU fallback: CPU tensors raise.
+The candidates come from the caller, from any matcher: stereo.depth_hint_candidates makes them on the GPU with the reference's
+twelve settings (the reference uses OpenCV SGBM on the host), and stereo.precompute_depth_hints chains it with this module.
+One HIP launch, no autograd, no CPU fallback: CPU tensors raise.
 """
 import torch
 
