@@ -727,6 +727,18 @@ typedef struct {
  * output channels; the B operand is gathered per lane through the coordinate-padding + mask test.  */
 int wmd_sparse_conv(const wmd_sparse_conv_args* args, void* stream);
 
+/* The table of instantiations behind wmd_sparse_conv: wmd_sparse_conv_config_name returns e.g.
+ * "sparse_conv_kernel<2,9,false,8,2,true>" (the kernel's template arguments MR,TAPS,DUAL,WK,UN,ROWS: the name the launch
+ * profile shows) or NULL when i is out of range.                                                                        */
+int wmd_sparse_conv_num_configs(void);
+const char* wmd_sparse_conv_config_name(int i);
+
+/* What wmd_sparse_conv would launch on this problem (host code: no HIP call, no pointer is dereferenced; wp2 != NULL is read
+ * as "dual-head mode" and nothing else): the table index of the instantiation, *grid_x (may be NULL) receives the launch's
+ * grid.x.  -1 with wmd_last_error() set to wmd_sparse_conv's own text for a problem that entry refuses (its null-pointer tests
+ * on the tensors aside); -1 with *grid_x = 0 and no error for max_out = 0, where wmd_sparse_conv launches nothing.           */
+int wmd_sparse_conv_plan(const wmd_sparse_conv_args* args, int* grid_x);
+
 /* ------------------------------------------------------------------ *
  * Multi-scale loss front-end
  * ------------------------------------------------------------------ */

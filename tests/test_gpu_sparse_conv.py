@@ -103,6 +103,10 @@ def launch(dev, c, k, coords, counts, max_out, pad, split_waves=0, nnz_stride=1)
     ran = {r["kernel"]: r["calls"] for r in _lib.profile_end()}
     want = {expected(c, max_out)["name"]: 1} if max_out > 0 else {}
     assert ran == want, "%s: the profile shows %s, expected %s" % (c["key"], ran, want)
+    # ... and the host's own answer for the same call (wmd_sparse_conv_plan) names it too, with the mirror's grid
+    planned = S.sparse_conv_plan(c["H"], c["W"], c["C1"], c["Cout"], c["ksize"], max_out, B=B, up1=c["up1"], C2=c["C2"], C1tot=c["C1tot"], c1_off=c["c1_off"],
+                                 dual=c["dual"], c1_off2=c["c1_off2"], pad=pad, act=c["act"], split_waves=split_waves)
+    assert planned == ((expected(c, max_out)["name"], expected(c, max_out)["grid_x"]) if max_out > 0 else (None, 0)), (c["key"], planned)
     SEEN.update(ran)
     return y, bufs
 

@@ -222,6 +222,9 @@ SIGNATURES = {
     "wmd_mask_level_lists": (C.c_int, [C.POINTER(MaskLevelArgs), C.c_void_p]),
     "wmd_conv_list_tile_supported": (C.c_int, [C.c_int, C.c_int]),
     "wmd_sparse_conv": (C.c_int, [C.POINTER(SparseConvArgs), C.c_void_p]),
+    "wmd_sparse_conv_num_configs": (C.c_int, []),
+    "wmd_sparse_conv_config_name": (C.c_char_p, [C.c_int]),
+    "wmd_sparse_conv_plan": (C.c_int, [C.POINTER(SparseConvArgs), C.POINTER(C.c_int)]),
     "wmd_upsample_bilinear_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_void_p]),
     "wmd_upsample_bilinear_bwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_void_p]),
     "wmd_eval_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -642,8 +642,26 @@ extern "C" int wmd_mask_threshold(const float* yh, const float* minmax, float th
     return check_launch("mask_threshold_kernel");
 }
 
-extern "C" int wmd_mask_dilate_multi(const uint8_t* mask, int h, int w, const wmd_dilate_spec* specs, int n, void* stream) {
-    return wmd_mask_dilate_multi_b(mask, 1, h, w, specs, n, stream);
+// ---- the three entries of mask_level_kernel: one initialiser, one shape check, one spec check, one launch ----------------------
+static MaskLevelKArgs mask_level_kargs(int h, int w, int n) {
+    MaskLevelKArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h = h;
+    a.w = w;
+    a.n = n;
+    a.tiles_x = (w + ML_T - 1) / ML_T;
+    return a;
+}
+
+// B, the map and the spec count under the entry's name.  n_yl (wmd_mask_level only): that entry words the batch and the map
+// separately, with its plane size between them
+static int mask_shape_ok(const char* who, int B, int h, int w, int n, const size_t* n_yl = nullptr) {
+    const bool bad_b = B <= 0 || B > 65535, bad_map = h <= 0 || w <= 0 || n <= 0 || n > 8;
+    if (!n_yl) return bad_b || bad_map ? fail(WMD_ERR_BAD_SHAPE, "%s: B=%d h=%d w=%d n=%d", who, B, h, w, n) : WMD_OK;
+    if (bad_b) return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d", who, B);
+    if (*n_yl == 0 || *n_yl > (size_t)1 << 24) return fail(WMD_ERR_BAD_SHAPE, "%s: n_yl=%zu", who, *n_yl);
+    if (bad_map) return fail(WMD_ERR_BAD_SHAPE, "%s: h=%d w=%d n=%d", who, h, w, n);
+    return WMD_OK;
 }
 
 static int mask_specs_ok(const char* who, const wmd_dilate_spec* specs, int n, int* max_up) {
@@ -656,24 +674,32 @@ static int mask_specs_ok(const char* who, const wmd_dilate_spec* specs, int n, i
     return WMD_OK;
 }
 
+// up: the largest of the specs; level_bytes: the launch reads the coefficient planes (16 bytes per coarse cell)
+static int mask_level_launch(const MaskLevelKArgs& a, bool from_mask, int B, int up, const char* prof_name, bool level_bytes, hipStream_t s) {
+    const double maxpix = (double)a.h * up * a.w * up;
+    ProfScope prof(prof_name, 25.0 * maxpix * a.n * B, (2.0 * maxpix * a.n + (level_bytes ? 16.0 * a.h * a.w : 0.0)) * B, s);
+    const dim3 grid(a.tiles_x * ((a.h + ML_T - 1) / ML_T), B, a.n);
+    if (from_mask) {
+        hipLaunchKernelGGL(mask_level_kernel<true>, grid, dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(mask_level_kernel<false>, grid, dim3(256), 0, s, a);
+    }
+    return check_launch(prof_name);
+}
+
+extern "C" int wmd_mask_dilate_multi(const uint8_t* mask, int h, int w, const wmd_dilate_spec* specs, int n, void* stream) {
+    return wmd_mask_dilate_multi_b(mask, 1, h, w, specs, n, stream);
+}
+
 extern "C" int wmd_mask_dilate_multi_b(const uint8_t* mask, int B, int h, int w, const wmd_dilate_spec* specs, int n, void* stream) {
     if (!mask || !specs) return fail(WMD_ERR_BAD_ARG, "wmd_mask_dilate_multi: null pointer");
-    if (B <= 0 || B > 65535 || h <= 0 || w <= 0 || n <= 0 || n > 8)
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_mask_dilate_multi: B=%d h=%d w=%d n=%d", B, h, w, n);
+    if (int st = mask_shape_ok("wmd_mask_dilate_multi", B, h, w, n)) return st;
     int up;
     if (int st = mask_specs_ok("wmd_mask_dilate_multi", specs, n, &up)) return st;
-    MaskLevelKArgs a;
-    memset(&a, 0, sizeof(a));
+    MaskLevelKArgs a = mask_level_kargs(h, w, n);
     a.mask0 = mask;
-    a.h = h;
-    a.w = w;
-    a.n = n;
-    a.tiles_x = (w + ML_T - 1) / ML_T;
     for (int i = 0; i < n; ++i) a.s[i] = specs[i];
-    const double maxpix = (double)h * up * w * up;
-    ProfScope prof("mask_dilate_multi_kernel", 25.0 * maxpix * n * B, 2.0 * maxpix * n * B, (hipStream_t)stream);
-    hipLaunchKernelGGL(mask_level_kernel<true>, dim3(a.tiles_x * ((h + ML_T - 1) / ML_T), B, n), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch("mask_dilate_multi_kernel");
+    return mask_level_launch(a, true, B, up, "mask_dilate_multi_kernel", false, (hipStream_t)stream);
 }
 
 extern "C" int wmd_mask_level(const float* yl, size_t n_yl, const float* yh, float thresh_ratio, int h, int w,
@@ -684,13 +710,10 @@ extern "C" int wmd_mask_level(const float* yl, size_t n_yl, const float* yh, flo
 extern "C" int wmd_mask_level_b(const float* yl, size_t n_yl, const float* yh, float thresh_ratio, int B, int h, int w,
                                 const wmd_dilate_spec* specs, int n, float* minmax_scratch, void* stream) {
     if (!yl || !yh || !specs) return fail(WMD_ERR_BAD_ARG, "wmd_mask_level: null pointer");
-    if (B <= 0 || B > 65535) return fail(WMD_ERR_BAD_SHAPE, "wmd_mask_level: B=%d", B);
-    if (n_yl == 0 || n_yl > (size_t)1 << 24) return fail(WMD_ERR_BAD_SHAPE, "wmd_mask_level: n_yl=%zu", n_yl);
-    if (h <= 0 || w <= 0 || n <= 0 || n > 8) return fail(WMD_ERR_BAD_SHAPE, "wmd_mask_level: h=%d w=%d n=%d", h, w, n);
+    if (int st = mask_shape_ok("wmd_mask_level", B, h, w, n, &n_yl)) return st;
     int up;
     if (int st = mask_specs_ok("wmd_mask_level", specs, n, &up)) return st;
-    MaskLevelKArgs a;
-    memset(&a, 0, sizeof(a));
+    MaskLevelKArgs a = mask_level_kargs(h, w, n);
     if (B > 1 && minmax_scratch) {   // one min/max launch per batch instead of a whole-plane reduction in every block of every frame
         hipLaunchKernelGGL(minmax_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, yl, n_yl, minmax_scratch);
         a.mm = minmax_scratch;
@@ -699,23 +722,15 @@ extern "C" int wmd_mask_level_b(const float* yl, size_t n_yl, const float* yh, f
     a.yh = yh;
     a.ratio = thresh_ratio;
     a.n_yl = (int)n_yl;
-    a.h = h;
-    a.w = w;
-    a.n = n;
-    a.tiles_x = (w + ML_T - 1) / ML_T;
     for (int i = 0; i < n; ++i) a.s[i] = specs[i];
-    const double maxpix = (double)h * up * w * up;
-    ProfScope prof("mask_level_kernel", 25.0 * maxpix * n * B, (2.0 * maxpix * n + 16.0 * h * w) * B, (hipStream_t)stream);
-    hipLaunchKernelGGL(mask_level_kernel<false>, dim3(a.tiles_x * ((h + ML_T - 1) / ML_T), B, n), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch("mask_level_kernel");
+    return mask_level_launch(a, false, B, up, "mask_level_kernel", true, (hipStream_t)stream);
 }
 
 extern "C" size_t wmd_mask_level_scratch_ints(int B) { return B > 0 ? (size_t)kMlFrame0 + (size_t)kMlFrameInts * B : 0; }
 
 extern "C" int wmd_mask_level_lists(const wmd_mask_level_args* g, void* stream) {
     if (!g || !g->specs || !g->scratch) return fail(WMD_ERR_BAD_ARG, "wmd_mask_level_lists: null pointer");
-    if (g->B <= 0 || g->B > 65535 || g->h <= 0 || g->w <= 0 || g->n <= 0 || g->n > 8)
-        return fail(WMD_ERR_BAD_SHAPE, "wmd_mask_level_lists: B=%d h=%d w=%d n=%d", g->B, g->h, g->w, g->n);
+    if (int st = mask_shape_ok("wmd_mask_level_lists", g->B, g->h, g->w, g->n)) return st;
     if (!g->mask0 && (!g->yl || !g->yh)) return fail(WMD_ERR_BAD_ARG, "wmd_mask_level_lists: neither a base mask nor yl / yh");
     if (!g->mask0 && (g->n_yl == 0 || g->n_yl > (size_t)1 << 24)) return fail(WMD_ERR_BAD_SHAPE, "wmd_mask_level_lists: n_yl=%zu", g->n_yl);
     if (g->ncounts < 0 || g->ncounts > 8) return fail(WMD_ERR_BAD_ARG, "wmd_mask_level_lists: ncounts=%d", g->ncounts);
@@ -723,12 +738,10 @@ extern "C" int wmd_mask_level_lists(const wmd_mask_level_args* g, void* stream) 
         (g->ring_slots <= 0 || g->counts_off < 0 || 1 + g->counts_off + g->B * g->ncounts > g->slot_ints))
         return fail(WMD_ERR_BAD_ARG, "wmd_mask_level_lists: counts do not fit a ring slot (off %d + %d x %d > %d ints)", g->counts_off,
                     g->B, g->ncounts, g->slot_ints - 1);
-    MaskLevelKArgs a;
-    memset(&a, 0, sizeof(a));
-    wmd_dilate_spec plain[8];
+    MaskLevelKArgs a = mask_level_kargs(g->h, g->w, g->n);
     for (int i = 0; i < g->n; ++i) {
         const wmd_level_spec& sp = g->specs[i];
-        plain[i] = wmd_dilate_spec{sp.up, sp.radius, sp.out, nullptr, 0};
+        a.s[i] = wmd_dilate_spec{sp.up, sp.radius, sp.out, nullptr, 0};
         if (sp.count < 0 || sp.count > g->ncounts) return fail(WMD_ERR_BAD_ARG, "wmd_mask_level_lists: spec %d count column %d", i, sp.count);
         if (sp.tile_h || sp.tile_w) {
             const int R = ML_T * sp.up;
@@ -740,8 +753,7 @@ extern "C" int wmd_mask_level_lists(const wmd_mask_level_args* g, void* stream) 
         a.ls[i] = MaskListSpec{sp.tile_h, sp.tile_w, sp.tile_list, sp.tile_count, sp.count, sp.and_mask};
     }
     int up;
-    if (int st = mask_specs_ok("wmd_mask_level_lists", plain, g->n, &up)) return st;
-    for (int i = 0; i < g->n; ++i) a.s[i] = plain[i];
+    if (int st = mask_specs_ok("wmd_mask_level_lists", a.s, g->n, &up)) return st;
     a.mask0 = g->mask0;
     a.yl = g->yl;
     a.yh = g->yh;
@@ -749,10 +761,6 @@ extern "C" int wmd_mask_level_lists(const wmd_mask_level_args* g, void* stream) 
     a.range_keys = g->range_keys;   // (an injected mask does not read them, but its last block re-arms them all the same)
     a.ratio = g->thresh_ratio;
     a.n_yl = (int)g->n_yl;
-    a.h = g->h;
-    a.w = g->w;
-    a.n = g->n;
-    a.tiles_x = (g->w + ML_T - 1) / ML_T;
     a.scratch = g->scratch;
     a.ring = g->ncounts > 0 ? g->counts : nullptr;
     a.ring_slots = g->ring_slots;
@@ -761,15 +769,7 @@ extern "C" int wmd_mask_level_lists(const wmd_mask_level_args* g, void* stream) 
     a.ncounts = g->ncounts;
     a.advance = g->advance;
     a.B = g->B;
-    const double maxpix = (double)g->h * up * g->w * up;
-    ProfScope prof("mask_level_kernel", 25.0 * maxpix * g->n * g->B, (2.0 * maxpix * g->n + 16.0 * g->h * g->w) * g->B, (hipStream_t)stream);
-    const dim3 grid(a.tiles_x * ((g->h + ML_T - 1) / ML_T), g->B, g->n);
-    if (g->mask0) {
-        hipLaunchKernelGGL(mask_level_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        hipLaunchKernelGGL(mask_level_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    return check_launch("mask_level_kernel");
+    return mask_level_launch(a, g->mask0 != nullptr, g->B, up, "mask_level_kernel", true, (hipStream_t)stream);
 }
 
 extern "C" int wmd_mask_compact_multi(const wmd_compact_spec* specs, int n, void* stream) {
@@ -792,20 +792,67 @@ extern "C" int wmd_mask_compact_multi_b(const wmd_compact_spec* specs, int n, in
     return check_launch("mask_compact_multi_kernel");
 }
 
-extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
+// ---- wmd_sparse_conv: the switches, the table of instantiations, the plan --------------------------------------------------------
+// Every switch of the gather-GEMM but WMD_SPARSE_PROF_SHAPES (development, read per profiled call), read once per process:
+struct SparseSwitches {
+    int split_waves;   // WMD_SPARSE_SPLIT_WAVES=<n>: what wmd_sparse_conv_args.split_waves = 0 stands for (2048)
+    int mr;            // WMD_SPARSE_MR=1|2|4 forces the out-channel tiles per block, clamped to the launch's (0: the rule below)
+    int grid;          // WMD_SPARSE_GRID=<n> overrides the total block target (development; 2048)
+    bool rows_off;     // WMD_SPARSE_ROWS=0: no row windows, every 3x3 launch gathers per tap
+};
+static const SparseSwitches& sparse_switches() {
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    static const SparseSwitches sw = {num("WMD_SPARSE_SPLIT_WAVES", 2048), num("WMD_SPARSE_MR", 0), num("WMD_SPARSE_GRID", 2048), num("WMD_SPARSE_ROWS", 1) == 0};
+    return sw;
+}
+
+struct SparseCfg {
+    int MR, TAPS, DUAL, WK, UN, ROWS;
+    const char* name;   // what the profile shows: the kernel with its template arguments
+    void (*launch)(const SparseKArgs&, dim3, hipStream_t);
+};
+template <int MR, int TAPS, bool DUAL, int WK, int UN, bool ROWS>
+static void sparse_conv_launch(const SparseKArgs& a, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((sparse_conv_kernel<MR, TAPS, DUAL, WK, UN, ROWS>), grid, dim3(64 * WK), 0, s, a);
+}
+#define WMD_SPARSE_CFG(MR_, TAPS_, DUAL_, WK_, UN_, ROWS_)                                                            \
+    {MR_, TAPS_, DUAL_, WK_, UN_, ROWS_, "sparse_conv_kernel<" #MR_ "," #TAPS_ "," #DUAL_ "," #WK_ "," #UN_ "," #ROWS_ ">", \
+     sparse_conv_launch<MR_, TAPS_, DUAL_, WK_, UN_, ROWS_>}
+// three families (3x3 with row windows, 3x3 on maps narrower than a window, 1x1), each at MR = 1, 2, 4 and in the dual form
+static const SparseCfg kSparseCfgs[] = {
+    WMD_SPARSE_CFG(1, 9, false, 8, 2, true),  WMD_SPARSE_CFG(2, 9, false, 8, 2, true),  WMD_SPARSE_CFG(4, 9, false, 8, 2, true),  WMD_SPARSE_CFG(1, 9, true, 8, 2, true),
+    WMD_SPARSE_CFG(1, 9, false, 8, 2, false), WMD_SPARSE_CFG(2, 9, false, 8, 2, false), WMD_SPARSE_CFG(4, 9, false, 8, 2, false), WMD_SPARSE_CFG(1, 9, true, 8, 2, false),
+    WMD_SPARSE_CFG(1, 1, false, 4, 8, false), WMD_SPARSE_CFG(2, 1, false, 4, 8, false), WMD_SPARSE_CFG(4, 1, false, 4, 8, false), WMD_SPARSE_CFG(1, 1, true, 4, 8, false),
+};
+#undef WMD_SPARSE_CFG
+constexpr int kNumSparseCfgs = sizeof(kSparseCfgs) / sizeof(kSparseCfgs[0]);
+
+struct SparsePlan {
+    int cfg;   // index into kSparseCfgs
+    dim3 grid;
+    SparseKArgs args;
+};
+
+// What wmd_sparse_conv and wmd_sparse_conv_plan refuse before anything else, in this order (tensors: the launch needs its pointers)
+static int sparse_conv_check(const wmd_sparse_conv_args* g, bool tensors) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: null args");
-    if (!g->x1 || !g->out_coords || !g->out_nnz || !g->wp || !g->y)
+    if (tensors && (!g->x1 || !g->out_coords || !g->out_nnz || !g->wp || !g->y))
         return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: null pointer");
-    if (g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: C2=%d but x2 is null", g->C2);
-    const int B = g->B > 1 ? g->B : 1;
-    const int st = conv_check_problem(B, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, g->act, "wmd_sparse_conv");
+    if (tensors && g->C2 > 0 && !g->x2) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: C2=%d but x2 is null", g->C2);
+    const int st = conv_check_problem(g->B > 1 ? g->B : 1, g->H, g->W, g->C1, g->up1, g->C2, g->Cout, g->ksize, g->pad_mode, g->act, "wmd_sparse_conv");
     if (st) return st;
     if (g->max_out < 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: max_out=%d", g->max_out);
     if (g->c1_off < 0 || g->c1_off + g->C1 > g->C1tot) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: channel slice");
     if (g->wp2 && (g->Cout > 16 || g->c1_off2 < 0 || g->c1_off2 + g->C1 > g->C1tot || g->C2 != 0))
         return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: dual-head mode needs Cout <= 16, C2 == 0 and a valid slice");
-    if (g->max_out == 0) return WMD_OK;
-    SparseKArgs a;
+    return WMD_OK;
+}
+
+// The launch of a checked problem with max_out > 0: the kernel's arguments, the instantiation and the grid.
+static int plan_sparse_conv(const wmd_sparse_conv_args* g, SparsePlan* p) {
+    const SparseSwitches& sw = sparse_switches();
+    const int B = g->B > 1 ? g->B : 1;
+    SparseKArgs& a = p->args;
     a.g = *g;
     const int Cin = g->C1 + g->C2;
     a.nci4 = ((Cin + 15) / 16) * 4;
@@ -815,56 +862,60 @@ extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
     a.plane1 = (size_t)(g->H / g->up1) * a.W1;
     if (B > 65535) return fail(WMD_ERR_BAD_SHAPE, "wmd_sparse_conv: B=%d", B);
     a.nnz_stride = B > 1 ? g->nnz_stride : 0;
-    static const int split_waves = [] { const char* e = getenv("WMD_SPARSE_SPLIT_WAVES"); return e ? atoi(e) : 2048; }();
     if (g->split_waves < 0) return fail(WMD_ERR_BAD_ARG, "wmd_sparse_conv: split_waves=%d", g->split_waves);
-    a.split_waves = g->split_waves > 0 ? g->split_waves : split_waves;
-    hipStream_t s = (hipStream_t)stream;
+    a.split_waves = g->split_waves > 0 ? g->split_waves : sw.split_waves;
     const int tiles = (g->max_out + 15) / 16;
     const int taps = g->ksize == 3 ? 9 : 1;
-    // the profile record carries the template arguments of the instantiation that ran (the launch macro below spells them);
-    // WMD_SPARSE_PROF_SHAPES (development) appends the layer shape: one profile line per shape
-    char pname[160];
-    const bool prof_shapes = g_prof_on && getenv("WMD_SPARSE_PROF_SHAPES");
-    auto prof_name = [&](const char* inst) -> const char* {
-        if (!prof_shapes) return inst;
-        snprintf(pname, sizeof(pname), "%s C%d+%d->%d k%d %dx%d%s", inst, g->C1, g->C2, g->Cout, g->ksize, g->H, g->W, g->wp2 ? " dual" : "");
-        return pname;
-    };
     // MR out-channel tiles per block: as few as keeps the grid near the machine size -- a sparse launch has far fewer
     // pixel tiles than the GPU has SIMDs, so out-channel tiles go to separate blocks (each re-gathers the same few
     // pixels out of L2) until the capacity grid reaches ~512 blocks (measured: tools/sparse_microbench.py); a full-density fine level keeps MR large and
-    // gathers once.  UN K-steps per wave are in flight together: the whole K-slice of a wave when registers allow.
-    static const int mr_force = [] { const char* e = getenv("WMD_SPARSE_MR"); return e ? atoi(e) : 0; }();
+    // gathers once.  A dual launch is the MR = 1 row of its family.
     int MR = 1;
     while (MR < 4 && MR < a.ncot && (long)tiles * B * ((a.ncot + MR - 1) / MR) > 512) MR *= 2;
-    if (mr_force == 1 || mr_force == 2 || mr_force == 4) MR = std::min(mr_force, a.ncot >= 4 ? 4 : a.ncot >= 2 ? 2 : 1);
-    // grid.x: enough blocks to fill the machine a few times over, never more than the capacity (a block walks further tasks
-    // itself); WMD_SPARSE_GRID overrides the total block target (development)
-    static const int grid_target = [] { const char* e = getenv("WMD_SPARSE_GRID"); return e ? atoi(e) : 2048; }();
-#define WMD_SPARSE_LAUNCH(MR_, TAPS_, DUAL_, WK_, UN_, ROWS_)                                                          \
-    do {                                                                                                               \
-        ProfScope prof(prof_name("sparse_conv_kernel<" #MR_ "," #TAPS_ "," #DUAL_ "," #WK_ "," #UN_ "," #ROWS_ ">"), 0.0, 0.0, s); \
-        hipLaunchKernelGGL((sparse_conv_kernel<MR_, TAPS_, DUAL_, WK_, UN_, ROWS_>),                                   \
-                           dim3(std::max(1, std::min(tiles, grid_target / (((a.ncot + MR_ - 1) / MR_) * B))), (a.ncot + MR_ - 1) / MR_, B), \
-                           dim3(64 * WK_), 0, s, a);                                                                   \
-    } while (0)
-    static const int rows_off = [] { const char* e = getenv("WMD_SPARSE_ROWS"); return e && atoi(e) == 0; }();
-    if (taps == 9 && g->W >= 3 && a.W1 >= 3 && !rows_off) {
-        if (g->wp2) WMD_SPARSE_LAUNCH(1, 9, true, 8, 2, true);
-        else if (MR == 4) WMD_SPARSE_LAUNCH(4, 9, false, 8, 2, true);
-        else if (MR == 2) WMD_SPARSE_LAUNCH(2, 9, false, 8, 2, true);
-        else WMD_SPARSE_LAUNCH(1, 9, false, 8, 2, true);
-    } else if (taps == 9) {   // maps narrower than a window
-        if (g->wp2) WMD_SPARSE_LAUNCH(1, 9, true, 8, 2, false);
-        else if (MR == 4) WMD_SPARSE_LAUNCH(4, 9, false, 8, 2, false);
-        else if (MR == 2) WMD_SPARSE_LAUNCH(2, 9, false, 8, 2, false);
-        else WMD_SPARSE_LAUNCH(1, 9, false, 8, 2, false);
-    } else {
-        if (g->wp2) WMD_SPARSE_LAUNCH(1, 1, true, 4, 8, false);
-        else if (MR == 4) WMD_SPARSE_LAUNCH(4, 1, false, 4, 8, false);
-        else if (MR == 2) WMD_SPARSE_LAUNCH(2, 1, false, 4, 8, false);
-        else WMD_SPARSE_LAUNCH(1, 1, false, 4, 8, false);
+    if (sw.mr == 1 || sw.mr == 2 || sw.mr == 4) MR = std::min(sw.mr, a.ncot >= 4 ? 4 : a.ncot >= 2 ? 2 : 1);
+    const bool dual = g->wp2 != nullptr;
+    if (dual) MR = 1;
+    const bool rows = taps == 9 && g->W >= 3 && a.W1 >= 3 && !sw.rows_off;   // else: a 1x1, or a map narrower than a window
+    // UN K-steps per wave are in flight together: the whole K-slice of a wave when registers allow
+    const int WK = taps == 9 ? 8 : 4, UN = taps == 9 ? 2 : 8;
+    p->cfg = 0;
+    for (const SparseCfg& c : kSparseCfgs)
+        if (c.MR == MR && c.TAPS == taps && c.DUAL == dual && c.WK == WK && c.UN == UN && c.ROWS == rows) p->cfg = (int)(&c - kSparseCfgs);
+    // grid.x: enough blocks to fill the machine a few times over, never more than the capacity (a block walks further tasks itself)
+    const int groups = (a.ncot + MR - 1) / MR;
+    p->grid = dim3(std::max(1, std::min(tiles, sw.grid / (groups * B))), groups, B);
+    return WMD_OK;
+}
+
+extern "C" int wmd_sparse_conv(const wmd_sparse_conv_args* g, void* stream) {
+    if (int st = sparse_conv_check(g, true)) return st;
+    if (g->max_out == 0) return WMD_OK;
+    SparsePlan p;
+    if (int st = plan_sparse_conv(g, &p)) return st;
+    const SparseCfg& cfg = kSparseCfgs[p.cfg];
+    // the profile record carries the template arguments of the instantiation that ran;
+    // WMD_SPARSE_PROF_SHAPES (development) appends the layer shape: one profile line per shape
+    char pname[160];
+    const char* name = cfg.name;
+    if (g_prof_on && getenv("WMD_SPARSE_PROF_SHAPES")) {
+        snprintf(pname, sizeof(pname), "%s C%d+%d->%d k%d %dx%d%s", cfg.name, g->C1, g->C2, g->Cout, g->ksize, g->H, g->W, g->wp2 ? " dual" : "");
+        name = pname;
     }
-#undef WMD_SPARSE_LAUNCH
+    {
+        ProfScope prof(name, 0.0, 0.0, (hipStream_t)stream);
+        cfg.launch(p.args, p.grid, (hipStream_t)stream);
+    }
     return check_launch("sparse_conv_kernel");
+}
+
+extern "C" int wmd_sparse_conv_num_configs(void) { return kNumSparseCfgs; }
+
+extern "C" const char* wmd_sparse_conv_config_name(int i) { return i >= 0 && i < kNumSparseCfgs ? kSparseCfgs[i].name : nullptr; }
+
+extern "C" int wmd_sparse_conv_plan(const wmd_sparse_conv_args* g, int* grid_x) {
+    if (grid_x) *grid_x = 0;
+    SparsePlan p;
+    if (sparse_conv_check(g, false) || g->max_out == 0 || plan_sparse_conv(g, &p)) return -1;
+    if (grid_x) *grid_x = (int)p.grid.x;
+    return p.cfg;
 }

@@ -51,6 +51,11 @@ def _spec_array(specs, outs, counts):
         for i, ((up, r), o) in enumerate(zip(specs, outs))])
 
 
+def _mask_outs(lead, h, w, specs, dev):
+    """one uint8 mask lead + [h*up, w*up] per spec (up = spec[0]), for the launch to fill"""
+    return [torch.empty(tuple(lead) + (h * spec[0], w * spec[0]), device=dev, dtype=torch.uint8) for spec in specs]
+
+
 def dilate_multi(mask, specs, counts=None):
     """mask uint8 [h,w] (or [B,h,w]: one mask per frame); specs = [(up, radius), ...] -> list of uint8 masks
     [h*up, w*up] (or [B,h*up,w*up]), one launch.  counts: see _spec_array."""
@@ -59,7 +64,7 @@ def dilate_multi(mask, specs, counts=None):
     B = mask.shape[0] if batched else 1
     h, w = mask.shape[-2:]
     mask = mask.contiguous()
-    outs = [torch.empty(((B,) if batched else ()) + (h * up, w * up), device=mask.device, dtype=torch.uint8) for up, _ in specs]
+    outs = _mask_outs((B,) if batched else (), h, w, specs, mask.device)
     arr = _spec_array(specs, outs, counts)
     check(_lib.lib().wmd_mask_dilate_multi_b(ptr(mask), B, h, w, arr, len(specs), current_stream()), "wmd_mask_dilate_multi")
     return outs
@@ -74,7 +79,7 @@ def mask_level(yl, yh, thresh_ratio, specs, counts=None):
     h, w = yh.shape[-2:]
     B = yh.shape[0] if yh.dim() == 5 else 1
     yl, yh = yl.contiguous(), yh.contiguous()
-    outs = [torch.empty(((B,) if B > 1 else ()) + (h * up, w * up), device=yh.device, dtype=torch.uint8) for up, _ in specs]
+    outs = _mask_outs((B,) if B > 1 else (), h, w, specs, yh.device)
     arr = _spec_array(specs, outs, counts)
     mm = torch.empty((B, 2), device=yh.device, dtype=torch.float32) if B > 1 else None
     check(_lib.lib().wmd_mask_level_b(ptr(yl), yl.numel() // B, ptr(yh), float(thresh_ratio), B, h, w, arr, len(specs), ptr(mm),
@@ -152,15 +157,13 @@ def mask_level_lists(state, B, h, w, specs, thresh_ratio=0.0, yl=None, yh=None, 
     None[, and_mask uint8 [B,h*up,w*up]]), ...] -> (masks [B,h*up,w*up] uint8, lists [(list, count, tile_h, tile_w) or None])."""
     _on_gpu(yl, yh, mask0)
     dev = state.scratch.device
-    outs, lists, arr = [], [], []
+    outs, lists, arr = _mask_outs((B,), h, w, specs, dev), [], []
     ncounts = 0
-    for j, spec in enumerate(specs):
+    for j, (spec, o) in enumerate(zip(specs, outs)):
         up, r, col, tile = spec[:4]
         andm = spec[4] if len(spec) > 4 else None
         if andm is not None and (andm.dtype != torch.uint8 or andm.numel() != B * h * up * w * up or not andm.is_contiguous()):
             raise _lib.WmdError("mask_level_lists: and_mask must be a contiguous uint8 [B,%d,%d] tensor" % (h * up, w * up))
-        o = torch.empty((B, h * up, w * up), device=dev, dtype=torch.uint8)
-        outs.append(o)
         ncounts = max(ncounts, col)
         if tile is not None:
             th, tw = tile
@@ -223,6 +226,22 @@ def sparse_conv(y, x1, wp, bias, cout, ksize, out_coords, out_nnz, max_out, x2=N
                             split_waves=int(split_waves), B=B, nnz_stride=int(nnz_stride))
     check(_lib.lib().wmd_sparse_conv(C.byref(a), current_stream()), "wmd_sparse_conv")
     return y
+
+
+def sparse_conv_plan(H, W, C1, Cout, ksize, max_out, B=1, up1=1, C2=0, C1tot=None, c1_off=0, dual=False, c1_off2=0, pad="reflect",
+                     act="none", split_waves=0):
+    """What sparse_conv would launch on a problem of these shapes -> (instantiation name as the profile shows it, grid.x), or
+    (None, 0) for max_out = 0, where nothing is launched; a problem sparse_conv would refuse raises WmdError with the same text
+    (the query answers both with -1, so max_out = 0 is always read as the empty launch).  Host code (wmd_sparse_conv_plan):
+    no tensors, no GPU."""
+    a = _lib.SparseConvArgs(H=H, W=W, C1=C1, up1=up1, C1tot=C1 if C1tot is None else C1tot, c1_off=c1_off, C2=C2, Cout=Cout, ksize=ksize,
+                            pad_mode=PAD[pad], act=ACT[act], max_out=int(max_out), wp2=1 if dual else None, c1_off2=c1_off2,
+                            split_waves=int(split_waves), B=B)
+    grid_x = C.c_int(0)
+    i = _lib.lib().wmd_sparse_conv_plan(C.byref(a), C.byref(grid_x))
+    if i < 0 and max_out != 0:
+        raise _lib.WmdError("wmd_sparse_conv_plan: %s" % _lib.lib().wmd_last_error().decode())
+    return (_lib.lib().wmd_sparse_conv_config_name(i).decode() if i >= 0 else None), grid_x.value
 
 
 class LazyOpsDict(dict):
