@@ -790,6 +790,10 @@ typedef struct {
     float* workspace;             /* wmd_eval_workspace_floats(B, H, W)                    */
     size_t workspace_floats;
 } wmd_eval_kitti_args;
+/* Floats of workspace (0 for a size < 1).  What the caller may read after the call is the prefix, in floats: two [B,H,W] planes (the
+ * resized depth and the ground truth, -1 outside the mask), [B] valid-pixel counts (int32), [B,2] medians (depth, ground truth: with median_scaling the
+ * applied ratio of image b is the second over the first, at float 2 B H W + B + 2 b).  What follows belongs to the library.
+ * NULL is WMD_ERR_BAD_ARG, a short workspace WMD_ERR_WORKSPACE; any float pointer is aligned enough.                             */
 size_t wmd_eval_workspace_floats(int B, int H, int W);
 int wmd_eval_kitti(const wmd_eval_kitti_args* args, void* stream);
 
@@ -828,8 +832,9 @@ int wmd_flip_postprocess(const float* l_disp, const float* r_disp, float* out, i
  *
  * Sizes: H, W >= 3 (WMD_ERR_BAD_SHAPE below); H * 2 * ceil(W / 64) <= 16384 -- the hysteresis keeps two bit planes of an
  * image in LDS; 480 x 640 needs 9600 -- and a radius of at most 12 taps (sigma <= 3.1): WMD_ERR_UNSUPPORTED beyond, before
- * any launch.  workspace: wmd_eval_dbe_workspace_bytes(B, H, W) bytes, 8-byte aligned (0 for a bad shape); a short one is
- * WMD_ERR_WORKSPACE before any HIP call.                                                                            */
+ * any launch.  workspace: wmd_eval_dbe_workspace_bytes(B, H, W) bytes, 8-byte aligned (0 for a bad shape): 832 B of state,
+ * 8 H W of smoothed image and three bit planes of 4 H * 2 ceil(W / 64) per image.  A short one is WMD_ERR_WORKSPACE, then a
+ * misaligned one WMD_ERR_BAD_ARG (as a NULL one), before any HIP call.                                                */
 size_t wmd_eval_dbe_workspace_bytes(int B, int H, int W);
 int wmd_eval_canny(const float* img, unsigned char* edges_u8, int B, int H, int W, double sigma, double low, double high,
                    void* workspace, size_t workspace_bytes, void* stream);
@@ -1047,7 +1052,8 @@ int wmd_nyu_inputs(const unsigned char* image_u8, const unsigned char* depth_u8,
  *   4. vmin == vmax: every pixel gets row 0.  Otherwise Normalize's in-place float32 array with float64 scalars:
  *        t = (float)((double)x - (double)vmin);  t = (float)((double)t / ((double)vmax - (double)vmin));  row as above.
  * Five launches (four when the size does not change).  workspace: wmd_viz_workspace_bytes(B, H, W) bytes (0 for a bad
- * shape; monotone in each argument); a short one is WMD_ERR_WORKSPACE.  Refused before any HIP call: a NULL disp, lut, rgb
+ * shape; monotone in each argument: 4 (8 + 3 * 2048) bytes of selection state per image, then 4 H W per image for the
+ * resized maps); a short one is WMD_ERR_WORKSPACE, tested before its alignment.  Refused before any HIP call: a NULL disp, lut, rgb
  * or workspace, a percentile outside [0, 100] or NaN, a misaligned workspace (WMD_ERR_BAD_ARG); a size < 1
  * (WMD_ERR_BAD_SHAPE); H W >= 2^31 or B > 65535 (WMD_ERR_UNSUPPORTED).
  *
@@ -1114,7 +1120,9 @@ int wmd_pose_head_bwd(const float* params, const float* means, const float* w, c
  *   block = blockSize (the window is 2 (block / 2) + 1 wide), cap = preFilterCap, uniq = uniquenessRatio, disp12 =
  *   disp12MaxDiff (<= 0 means 1), directions 5 or 8; speckle_win == 0 skips the speckle stage.
  * workspace: wmd_stereo_sgbm_workspace_bytes(...) bytes, 256-byte aligned, at most about 1 GiB: images that do not fit
- * run in several groups inside the call.  The query returns 0 for arguments the entry refuses.
+ * run in several groups inside the call.  The query returns 0 for arguments the entry refuses.  Per image of a group, each
+ * rounded up to 256 bytes and in this order, every region holding the whole group: 16 H W C (prefiltered pairs), 2 H Wv D twice
+ * (the two volumes, Wv = W - min_disp - num_disp, D = num_disp), 4 H W (keys), 2 H W (the first map), 8 H W (speckle scratch).
  * Refused before any HIP call: a NULL left / right / disp / workspace, C not 1 or 3, min_disp < 0, num_disp not a multiple
  * of 16 in 16..256, block < 1, P1 < 0 or P1 > P2, directions not 5 or 8, uniq outside 0..100, a negative cap or speckle
  * setting (WMD_ERR_BAD_ARG); a size < 1 or W <= min_disp + num_disp (WMD_ERR_BAD_SHAPE); a short or misaligned workspace
@@ -1130,7 +1138,8 @@ int wmd_stereo_sgbm(const unsigned char* left, const unsigned char* right, const
 /* The speckle stage on its own, in place on disp int16 [B,H,W]: every 4-connected component -- neighbours both different
  * from `invalid` and at most max_diff apart; a chain of such steps is one component whatever its ends differ by -- of at
  * most max_size pixels becomes `invalid`.  Union-find over the whole map: a component may cross anything.  workspace:
- * wmd_stereo_filter_speckles_workspace_bytes(B, H, W) bytes (0 for a bad shape).  Four launches.                         */
+ * wmd_stereo_filter_speckles_workspace_bytes(B, H, W) bytes = 8 B H W rounded up to 256 (0 for a bad shape), 4-byte aligned;
+ * NULL is WMD_ERR_BAD_ARG, short or misaligned WMD_ERR_WORKSPACE.  Four launches.                                         */
 size_t wmd_stereo_filter_speckles_workspace_bytes(int B, int H, int W);
 int wmd_stereo_filter_speckles(short* disp, int B, int H, int W, int invalid, int max_size, int max_diff, void* workspace,
                                size_t workspace_bytes, void* stream);

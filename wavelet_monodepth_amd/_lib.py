@@ -325,6 +325,35 @@ def current_stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def require_device(who, **named):
+    """name=(tensor, dtype or tuple of dtypes or None for any[, note]): anything but None or such a device tensor raises WmdError"""
+    import torch
+
+    for name, (t, dtypes, *note) in named.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise WmdError("%s runs on the GPU only (%s is %s)" % (who, name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
+        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+        if dtypes != (None,) and t.dtype not in dtypes:
+            raise WmdError("%s: %s must be %s (got %s)%s" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype,
+                                                            ": " + note[0] if note else ""))
+
+
+def byte_workspace(nbytes, device):
+    """(a fresh int64 tensor of at least nbytes bytes and at least one word, nbytes); on the device at least 256-byte aligned"""
+    import torch
+
+    return torch.empty((max(nbytes, 8) + 7) // 8, device=device, dtype=torch.int64), nbytes
+
+
+def float_workspace(nfloats, device):
+    """a fresh float32 [nfloats]; None -- NULL to the entry, as an empty tensor's pointer is -- when the query answers 0"""
+    import torch
+
+    return torch.empty(nfloats, device=device, dtype=torch.float32) if nfloats else None
+
+
 def profile_begin():
     check(lib().wmd_profile_begin(), "wmd_profile_begin")
 

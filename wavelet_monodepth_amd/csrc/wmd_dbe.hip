@@ -24,13 +24,13 @@
 #include <cstdint>
 #include "wmd_internal.h"
 #include "wmd_select.h"
+#include "wmd_ws_layouts.h"
 
 namespace wmd {
 
 constexpr int DBE_MAX_RADIUS = 12;              // Gaussian taps 2 * 12 + 1: sigma up to 3.1
 constexpr int DBE_TH = 16, DBE_TW = 64;         // tile of the smoothing and suppression kernels: one wavefront per row
 constexpr int DBE_PLANE_WORDS = 16384;          // 64 KiB of LDS per bit plane in the hysteresis (two planes)
-constexpr int DBE_STATE = 208;                  // uint32 per image: min key, max key, n_est, n_gt, histA[101], histB[101]
 constexpr int DBE_HA = 4, DBE_HB = 105, DBE_NBIN = 101;
 constexpr double DBE_EPS = 2.220446049250313e-16;
 
@@ -348,27 +348,6 @@ __global__ void dbe_finish_kernel(const unsigned* __restrict__ state, float* __r
 
 static inline int dbe_wp(int W) { return 2 * ((W + 63) / 64); }
 
-struct DbeWs {
-    unsigned* state;
-    double* sm;
-    unsigned *weak, *strong, *gt;
-};
-
-static size_t dbe_carve(void* ws, int B, int H, int W, DbeWs* out) {
-    const size_t state = (size_t)B * DBE_STATE * sizeof(unsigned);          // a multiple of 8
-    const size_t sm = (size_t)B * H * W * sizeof(double);
-    const size_t plane = (size_t)B * H * dbe_wp(W) * sizeof(unsigned);
-    if (out) {
-        char* p = static_cast<char*>(ws);
-        out->state = reinterpret_cast<unsigned*>(p);
-        out->sm = reinterpret_cast<double*>(p + state);
-        out->weak = reinterpret_cast<unsigned*>(p + state + sm);
-        out->strong = reinterpret_cast<unsigned*>(p + state + sm + plane);
-        out->gt = reinterpret_cast<unsigned*>(p + state + sm + 2 * plane);
-    }
-    return state + sm + 3 * plane;
-}
-
 // shape and size rules shared by the two entry points; 0 = fine
 static int dbe_check_shape(const char* fn, int B, int H, int W) {
     if (B <= 0 || H < 3 || W < 3) return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d (needs B >= 1 and H, W >= 3)", fn, B, H, W);
@@ -427,40 +406,36 @@ using namespace wmd;
 
 extern "C" size_t wmd_eval_dbe_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H < 3 || W < 3) return 0;
-    return dbe_carve(nullptr, B, H, W, nullptr);
+    return dbe_layout(nullptr, B, H, W, dbe_wp(W)).bytes;
 }
 
 extern "C" int wmd_eval_canny(const float* img, unsigned char* edges_u8, int B, int H, int W, double sigma, double low, double high,
                               void* workspace, size_t workspace_bytes, void* stream) {
-    if (!img || !edges_u8 || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_eval_canny: null pointer");
+    if (!img || !edges_u8 || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_eval_canny: null pointer (img, edges_u8 or workspace)");
     int st = dbe_check_shape("wmd_eval_canny", B, H, W);
     if (st) return st;
     DbeTaps taps;
     st = dbe_taps("wmd_eval_canny", sigma, &taps);
     if (st) return st;
-    const size_t need = wmd_eval_dbe_workspace_bytes(B, H, W);
-    if (workspace_bytes < need) return fail(WMD_ERR_WORKSPACE, "wmd_eval_canny: workspace %zu < %zu bytes", workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(WMD_ERR_BAD_ARG, "wmd_eval_canny: workspace must be 8-byte aligned");
-    DbeWs ws;
-    dbe_carve(workspace, B, H, W, &ws);
+    st = check_workspace("wmd_eval_canny", workspace, workspace_bytes, wmd_eval_dbe_workspace_bytes(B, H, W), 8, WMD_ERR_BAD_ARG);
+    if (st) return st;
+    const DbeWs ws = dbe_layout(workspace, B, H, W, dbe_wp(W));
     return dbe_detect("wmd_eval_canny", img, nullptr, edges_u8, B, H, W, taps, low, high, ws, false, (hipStream_t)stream);
 }
 
 extern "C" int wmd_eval_dbe(const float* pred, const unsigned char* edges_gt_u8, const unsigned char* mask_u8, float* out2,
                             unsigned char* edges_est_u8, int B, int H, int W, double low, double high, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    if (!pred || !edges_gt_u8 || !out2 || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_eval_dbe: null pointer");
+    if (!pred || !edges_gt_u8 || !out2 || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_eval_dbe: null pointer (pred, edges_gt_u8, out2 or workspace)");
     int st = dbe_check_shape("wmd_eval_dbe", B, H, W);
     if (st) return st;
-    const size_t need = wmd_eval_dbe_workspace_bytes(B, H, W);
-    if (workspace_bytes < need) return fail(WMD_ERR_WORKSPACE, "wmd_eval_dbe: workspace %zu < %zu bytes", workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(WMD_ERR_BAD_ARG, "wmd_eval_dbe: workspace must be 8-byte aligned");
+    st = check_workspace("wmd_eval_dbe", workspace, workspace_bytes, wmd_eval_dbe_workspace_bytes(B, H, W), 8, WMD_ERR_BAD_ARG);
+    if (st) return st;
+    const DbeWs ws = dbe_layout(workspace, B, H, W, dbe_wp(W));
     DbeTaps taps;
     st = dbe_taps("wmd_eval_dbe", std::sqrt(2.0), &taps);
     if (st) return st;
     hipStream_t s = (hipStream_t)stream;
-    DbeWs ws;
-    dbe_carve(workspace, B, H, W, &ws);
     st = dbe_detect("wmd_eval_dbe", pred, edges_gt_u8, edges_est_u8, B, H, W, taps, low, high, ws, true, s);
     if (st) return st;
     const int Wp = dbe_wp(W);

@@ -21,6 +21,7 @@
 #include <cstdint>
 #include "wmd_internal.h"
 #include "wmd_select.h"
+#include "wmd_ws_layouts.h"
 
 namespace wmd {
 
@@ -203,26 +204,22 @@ using namespace wmd;
 
 extern "C" size_t wmd_eval_workspace_floats(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    // two masked planes, [B] counts (int), [B,2] medians, [B,2] selection states (three histograms each)
-    // + [B,64,9] fp64 partial error sums (and one float of slack to align them to 8 bytes)
-    return (size_t)B * H * W * 2 + (size_t)B * 3 + (size_t)B * 2 * SEL_STATE + (size_t)B * 64 * 9 * 2 + 2;
+    return eval_layout(nullptr, B, (size_t)H * W).bytes / sizeof(float);
 }
 
 extern "C" int wmd_eval_kitti(const wmd_eval_kitti_args* g, void* stream) {
     if (!g) return fail(WMD_ERR_BAD_ARG, "wmd_eval_kitti: null args");
-    if (!g->pred_disp || !g->gt_depth || !g->out || !g->workspace) return fail(WMD_ERR_BAD_ARG, "wmd_eval_kitti: null pointer");
+    if (!g->pred_disp || !g->gt_depth || !g->out || !g->workspace) return fail(WMD_ERR_BAD_ARG, "wmd_eval_kitti: null pointer (a tensor or the workspace)");
     if (g->B <= 0 || g->h <= 0 || g->w <= 0 || g->H <= 0 || g->W <= 0)
         return fail(WMD_ERR_BAD_SHAPE, "wmd_eval_kitti: B=%d h=%d w=%d H=%d W=%d", g->B, g->h, g->w, g->H, g->W);
     if (g->mask_mode < 0 || g->mask_mode > 1) return fail(WMD_ERR_BAD_ARG, "wmd_eval_kitti: mask_mode=%d", g->mask_mode);
     if ((double)g->H * g->W > 2147483647.0) return fail(WMD_ERR_UNSUPPORTED, "wmd_eval_kitti: more than 2^31 pixels per image");
-    const size_t need = wmd_eval_workspace_floats(g->B, g->H, g->W);
-    if (g->workspace_floats < need) return fail(WMD_ERR_WORKSPACE, "wmd_eval_kitti: workspace %zu < %zu floats", g->workspace_floats, need);
+    if (int st = check_workspace_floats("wmd_eval_kitti", g->workspace, g->workspace_floats, wmd_eval_workspace_floats(g->B, g->H, g->W))) return st;
     hipStream_t s = (hipStream_t)stream;
     const size_t plane = (size_t)g->H * g->W;
-    float* pd = g->workspace;
-    float* gm = pd + (size_t)g->B * plane;
-    int* count = reinterpret_cast<int*>(gm + (size_t)g->B * plane);
-    float* med = reinterpret_cast<float*>(count + g->B);
+    const EvalWs ws = eval_layout(g->workspace, g->B, plane);
+    float *pd = ws.pred, *gm = ws.gt, *med = ws.med;
+    int* count = ws.count;
     if (hipMemsetAsync(count, 0, sizeof(int) * g->B, s) != hipSuccess) return fail(WMD_ERR_HIP, "wmd_eval_kitti: hipMemsetAsync failed");
     {
         ProfScope prof("eval_prepare_kernel", 12.0 * g->B * plane, 4.0 * g->B * (3.0 * plane + (double)g->h * g->w), s);
@@ -232,7 +229,7 @@ extern "C" int wmd_eval_kitti(const wmd_eval_kitti_args* g, void* stream) {
     }
     int st = check_launch("eval_prepare_kernel");
     if (st) return st;
-    unsigned* state = reinterpret_cast<unsigned*>(med + 2 * g->B);
+    unsigned* state = ws.state;
     const size_t state_words = (size_t)g->B * 2 * SEL_STATE;
     if (g->median_scaling) {
         if (hipMemsetAsync(state, 0, sizeof(unsigned) * state_words, s) != hipSuccess)
@@ -259,12 +256,10 @@ extern "C" int wmd_eval_kitti(const wmd_eval_kitti_args* g, void* stream) {
         if (st) return st;
     }
     const int mblk = (int)std::max<size_t>(1, std::min<size_t>((plane + 8191) / 8192, 64));
-    float* after = reinterpret_cast<float*>(state + state_words);
-    double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(after) + 7) & ~(uintptr_t)7);
     ProfScope prof("eval_metrics_kernel", 30.0 * g->B * plane, 8.0 * g->B * plane, s);
-    hipLaunchKernelGGL(eval_metrics_kernel, dim3(mblk, g->B), dim3(1024), 0, s, pd, gm, med, g->out, partial, plane, g->median_scaling,
+    hipLaunchKernelGGL(eval_metrics_kernel, dim3(mblk, g->B), dim3(1024), 0, s, pd, gm, med, g->out, ws.partial, plane, g->median_scaling,
                        g->min_depth, g->max_depth, 1);
-    if (mblk > 1) hipLaunchKernelGGL(eval_metrics_finish_kernel, dim3(g->B), dim3(64), 0, s, partial, g->out, g->B, mblk);
+    if (mblk > 1) hipLaunchKernelGGL(eval_metrics_finish_kernel, dim3(g->B), dim3(64), 0, s, ws.partial, g->out, g->B, mblk);
     return check_launch("eval_metrics_kernel");
 }
 

@@ -179,9 +179,7 @@ extern "C" int wmd_depth_hints_fuse(const float* cand, int cand_is_disparity, fl
     if (C > 3) return fail(WMD_ERR_UNSUPPORTED, "%s: C=%d channels, at most 3", who, C);
     if (B > 65535 || H > 65535 * kHintTH || (double)B * std::max(M, C) * H * W > 2147483647.0)
         return fail(WMD_ERR_UNSUPPORTED, "%s: more than 2^31 elements, B > 65535 or H > %d", who, 65535 * kHintTH);
-    const size_t need = wmd_depth_hints_workspace_floats(B, M, H, W);
-    if (workspace_floats < need || (workspace_floats > 0 && !workspace))
-        return fail(WMD_ERR_WORKSPACE, "%s: workspace %zu floats at %p, %zu needed", who, workspace_floats, (void*)workspace, need);
+    if (int st = check_workspace_floats(who, workspace, workspace_floats, wmd_depth_hints_workspace_floats(B, M, H, W))) return st;
     hipStream_t s = (hipStream_t)stream;
     const double n = (double)B * H * W;
     ProfScope prof("hints_fuse_kernel", n * M * (80.0 + 75.0 * C), 4.0 * n * (M * (losses ? 2.0 : 1.0) + C + 2.0), s);

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include "wmd_internal.h"
 #include "wmd_resample.h"
+#include "wmd_ws_layouts.h"
 
 #pragma clang fp contract(off)
 
@@ -41,7 +42,7 @@ struct PyrLevel : ResampleTables {
 struct PyrPlan {
     int S;
     PyrLevel l[kMaxScales];
-    size_t table_ints, pixels, ws_bytes;
+    size_t table_ints, pixels;
 };
 
 static size_t level_lds(int rows, int ksh, int ksv, int th) { return ((size_t)rows * kTileW * 3 + 3) / 4 * 4 + 4 * ((size_t)kTileW * ksh + (size_t)th * ksv); }
@@ -83,7 +84,6 @@ static int pyr_plan(int N, int H0, int W0, int height, int width, int S, PyrPlan
         hi = l.h;
         wi = l.w;
     }
-    p.ws_bytes = 8 * (size_t)S * N;
     return WMD_OK;
 }
 
@@ -380,7 +380,7 @@ extern "C" int wmd_color_pyramid_tables(int H0, int W0, int height, int width, i
 extern "C" size_t wmd_color_pyramid_workspace_bytes(int N, int H0, int W0, int height, int width, int num_scales) {
     PyrPlan p;
     char why[256];
-    return pyr_plan(N, H0, W0, height, width, num_scales, p, why, sizeof(why)) == WMD_OK ? p.ws_bytes : 0;
+    return pyr_plan(N, H0, W0, height, width, num_scales, p, why, sizeof(why)) == WMD_OK ? array_layout<unsigned long long>(nullptr, (size_t)p.S * N).bytes : 0;
 }
 
 static int jitter_args(const char* who, const unsigned char* enable, const unsigned char* order, const float* factors, const int* hue_shift,
@@ -405,12 +405,12 @@ extern "C" int wmd_color_pyramid(const unsigned char* frames, int N, int H0, int
     PyrPlan p;
     char why[256];
     if (int st = pyr_plan(N, H0, W0, height, width, num_scales, p, why, sizeof(why))) return fail(st, "%s: %s", who, why);
-    if (!workspace || workspace_bytes < p.ws_bytes || ((size_t)workspace & 7))
-        return fail(WMD_ERR_WORKSPACE, "%s: workspace %zu bytes at %p, %zu needed (8-byte aligned)", who, workspace_bytes, workspace, p.ws_bytes);
+    const size_t need = array_layout<unsigned long long>(nullptr, (size_t)p.S * N).bytes;
+    if (int st = check_workspace(who, workspace, workspace_bytes, need, 8, WMD_ERR_WORKSPACE)) return st;
+    unsigned long long* sums = array_layout<unsigned long long>(workspace, (size_t)p.S * N).p;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
     if (enable) {
-        hipError_t e = hipMemsetAsync(sums, 0, p.ws_bytes, s);
+        hipError_t e = hipMemsetAsync(sums, 0, need, s);
         if (e != hipSuccess) return fail(WMD_ERR_HIP, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
     }
     FinishArgs f = {};
@@ -453,7 +453,7 @@ static bool jitter_shape_ok(int N, int h, int w) { return N >= 1 && h >= 1 && w 
 static bool jitter_shape_supported(int N, int h, int w) { return N <= 65535 && (double)h * w < 2147483648.0; }
 
 extern "C" size_t wmd_color_jitter_workspace_bytes(int N, int h, int w) {
-    return jitter_shape_ok(N, h, w) && jitter_shape_supported(N, h, w) ? 8 * (size_t)N : 0;
+    return jitter_shape_ok(N, h, w) && jitter_shape_supported(N, h, w) ? array_layout<unsigned long long>(nullptr, N).bytes : 0;
 }
 
 extern "C" int wmd_color_jitter(const unsigned char* images, unsigned char* out, int N, int h, int w, const unsigned char* enable,
@@ -465,11 +465,10 @@ extern "C" int wmd_color_jitter(const unsigned char* images, unsigned char* out,
     if (int st = jitter_args(who, enable, order, factors, hue_shift, jit)) return st;
     if (!jitter_shape_ok(N, h, w)) return fail(WMD_ERR_BAD_SHAPE, "%s: N=%d h=%d w=%d must be positive", who, N, h, w);
     if (!jitter_shape_supported(N, h, w)) return fail(WMD_ERR_UNSUPPORTED, "%s: N=%d above 65535 or h*w=%.0f at or above 2^31", who, N, (double)h * w);
-    const size_t need = 8 * (size_t)N;
-    if (!workspace || workspace_bytes < need || ((size_t)workspace & 7))
-        return fail(WMD_ERR_WORKSPACE, "%s: workspace %zu bytes at %p, %zu needed (8-byte aligned)", who, workspace_bytes, workspace, need);
+    const size_t need = wmd_color_jitter_workspace_bytes(N, h, w);
+    if (int st = check_workspace(who, workspace, workspace_bytes, need, 8, WMD_ERR_WORKSPACE)) return st;
+    unsigned long long* sums = array_layout<unsigned long long>(workspace, N).p;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
     hipError_t e = hipMemsetAsync(sums, 0, need, s);
     if (e != hipSuccess) return fail(WMD_ERR_HIP, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
     const size_t hw = (size_t)h * w;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <type_traits>
 #include <utility>
@@ -25,6 +26,39 @@ inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(WMD_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return WMD_OK;
+}
+
+// A caller's workspace, described once per entry (wmd_ws_layouts.h): a layout function takes the regions in order; the size query runs it on
+// a null base, the launch on the caller's pointer, of which the entry's check guarantees `base_align`.  A region aligned beyond that (fp64
+// partials in a float workspace) gets `align` spare bytes and its real address rounded up.  take<char>(0, a) only pads the offset to a.
+struct WsLayout {
+    char* base;
+    size_t base_align, off = 0;
+    WsLayout(void* ws, size_t guaranteed_align) : base(static_cast<char*>(ws)), base_align(guaranteed_align) {}
+    template <class T>
+    T* take(size_t count, size_t align = alignof(T)) {
+        const bool spare = count && align > base_align;   // otherwise offsets round relative to the base
+        const uintptr_t real = spare ? reinterpret_cast<uintptr_t>(base) : 0;
+        const size_t at = (real + off + align - 1) / align * align - real;
+        off = (spare ? off + align : at) + count * sizeof(T);
+        return base ? reinterpret_cast<T*>(base + at) : nullptr;
+    }
+    size_t bytes() const { return off; }
+};
+
+// The one workspace refusal: NULL, then short (both WMD_ERR_WORKSPACE), then misaligned -- with the entry's documented answer (include/wmd.h:
+// WMD_ERR_BAD_ARG for the colour images and the depth-boundary errors, WMD_ERR_WORKSPACE elsewhere).  An entry that answers a NULL workspace
+// with WMD_ERR_BAD_ARG refuses it with its other pointers, before this.  NULL passes only where nothing is needed and nothing is claimed.
+inline int check_workspace(const char* who, const void* ws, size_t have, size_t need, size_t align, int misaligned_status) {
+    const bool null = !ws && (have || need), misaligned = reinterpret_cast<uintptr_t>(ws) % align != 0;
+    if (!null && have >= need && !misaligned) return WMD_OK;
+    return fail(null || have < need ? WMD_ERR_WORKSPACE : misaligned_status, "%s: workspace %zu bytes at %p, %zu needed, %zu-byte aligned", who, have, ws,
+                need, align);
+}
+// the entries that count floats: no alignment is asked of a float pointer
+inline int check_workspace_floats(const char* who, const float* ws, size_t have, size_t need) {
+    const size_t cap = ~(size_t)0 / sizeof(float);
+    return check_workspace(who, ws, (have < cap ? have : cap) * sizeof(float), need * sizeof(float), 1, WMD_ERR_WORKSPACE);
 }
 
 constexpr int kNumCU = 256;  // MI355X

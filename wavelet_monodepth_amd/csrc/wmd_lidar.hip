@@ -22,26 +22,11 @@
 // 16 B per point = 1.9 MB and touches four words per valid point, the resolve reads the 11.2 MB back and writes 1.9 MB.
 #include <algorithm>
 #include "wmd_internal.h"
+#include "wmd_ws_layouts.h"
 
 namespace wmd {
 
 constexpr int kLidarThreads = 256;
-
-struct LidarWorkspace {   // all sizes in 64-bit words; zero region first, ones region after it
-    size_t pix, count, first, kmin, zero_words, total_words;
-};
-
-static LidarWorkspace lidar_layout(size_t B, size_t H, size_t W) {
-    const size_t hw = H * W, nk = H * (W - 1) + 1;
-    LidarWorkspace l;
-    l.pix = 0;                              // [B][hw] 64-bit
-    l.count = B * hw;                       // [B][nk] 32-bit
-    l.zero_words = l.count + (B * nk + 1) / 2;
-    l.first = l.zero_words;                 // [B][nk] 64-bit
-    l.kmin = l.first + B * nk;              // [B][nk] 32-bit
-    l.total_words = l.kmin + (B * nk + 1) / 2;
-    return l;
-}
 
 // ((P0 x + P1 y) + P2 z) + P3 with every product and sum rounded on its own.  hipcc contracts a * b + c into a fused
 // multiply-add by default -- also through __dmul_rn / __dadd_rn, which are plain operators in HIP -- and a fused row moves
@@ -121,7 +106,7 @@ static bool lidar_shape_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0
 
 extern "C" size_t wmd_lidar_depth_workspace_bytes(int B, int H, int W) {
     if (!lidar_shape_ok(B, H, W) || (double)H * W >= 2147483648.0) return 0;
-    return lidar_layout(B, H, W).total_words * sizeof(unsigned long long);
+    return lidar_layout(nullptr, B, H, W).bytes;
 }
 
 extern "C" int wmd_lidar_depth_maps(const float* points, const long long* offsets, const double* P, size_t total_points, int B, int H,
@@ -132,28 +117,26 @@ extern "C" int wmd_lidar_depth_maps(const float* points, const long long* offset
     if ((size_t)points & 15) return fail(WMD_ERR_BAD_ARG, "%s: points at %p, rows must be 16-byte aligned", who, (const void*)points);
     if ((double)H * W >= 2147483648.0 || total_points >= 2147483648ull)
         return fail(WMD_ERR_UNSUPPORTED, "%s: H*W=%.0f pixels, %zu points: both must stay below 2^31", who, (double)H * W, total_points);
-    const LidarWorkspace l = lidar_layout(B, H, W);
-    const size_t need = l.total_words * sizeof(unsigned long long);
-    if (!workspace || workspace_bytes < need || ((size_t)workspace & 7))
-        return fail(WMD_ERR_WORKSPACE, "%s: workspace %zu bytes at %p, %zu needed (8-byte aligned)", who, workspace_bytes, workspace, need);
+    if (int st = check_workspace(who, workspace, workspace_bytes, lidar_layout(nullptr, B, H, W).bytes, 8, WMD_ERR_WORKSPACE)) return st;
+    const LidarWs l = lidar_layout(workspace, B, H, W);
+    const size_t total_words = l.bytes / 8;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* ws = (unsigned long long*)workspace;
     const size_t cap = (size_t)kNumCU * 16;   // grid-stride loops: at most 16 blocks of 256 threads per CU
     auto blocks = [cap](size_t n) { return (unsigned)std::min(cap, (n + kLidarThreads - 1) / kLidarThreads); };
     {
-        ProfScope prof("lidar_init_kernel", 0.0, 8.0 * l.total_words, s);
-        hipLaunchKernelGGL(lidar_init_kernel, dim3(blocks(l.total_words)), dim3(kLidarThreads), 0, s, ws, l.zero_words, l.total_words);
+        ProfScope prof("lidar_init_kernel", 0.0, 8.0 * total_words, s);
+        hipLaunchKernelGGL(lidar_init_kernel, dim3(blocks(total_words)), dim3(kLidarThreads), 0, s, l.pix, l.zero_words, total_words);
     }
     if (total_points > 0) {
         ProfScope prof("lidar_scatter_kernel", 30.0 * (double)total_points, 16.0 * (double)total_points, s);
         // one row per thread (at most 2^23 blocks): the rows are independent and each waits on a chain of dependent loads
         hipLaunchKernelGGL(lidar_scatter_kernel, dim3((unsigned)((total_points + kLidarThreads - 1) / kLidarThreads)), dim3(kLidarThreads), 0, s, (const float4*)points, offsets, P, B, H, W,
-                           vel_depth, (long long)total_points, ws + l.pix, (unsigned*)(ws + l.count), ws + l.first, (unsigned*)(ws + l.kmin));
+                           vel_depth, (long long)total_points, l.pix, l.count, l.first, l.kmin);
     }
     {
-        ProfScope prof("lidar_resolve_kernel", 0.0, 8.0 * l.total_words + 4.0 * B * H * W, s);
-        hipLaunchKernelGGL(lidar_resolve_kernel, dim3(blocks((size_t)B * H * W)), dim3(kLidarThreads), 0, s, ws + l.pix, (const unsigned*)(ws + l.count),
-                           ws + l.first, (const unsigned*)(ws + l.kmin), depth, B, H, W);
+        ProfScope prof("lidar_resolve_kernel", 0.0, 8.0 * total_words + 4.0 * B * H * W, s);
+        hipLaunchKernelGGL(lidar_resolve_kernel, dim3(blocks((size_t)B * H * W)), dim3(kLidarThreads), 0, s, l.pix, l.count, l.first, l.kmin, depth, B, H,
+                           W);
     }
     return check_launch("lidar kernels");
 }

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include "wmd_internal.h"
+#include "wmd_ws_layouts.h"
 #include "wmd_photo_common.h"   // refl1, ssim_window / ssim_value, warp_P / warp_geom / clip_coord (shared with wmd_hints.hip)
 
 namespace wmd {
@@ -129,7 +130,7 @@ extern "C" int wmd_ssim_fwd(const float* x, const float* y, float* out, int B, i
 }
 
 extern "C" size_t wmd_ssim_bwd_workspace_floats(int B, int C, int H, int W) {
-    return (B > 0 && C > 0 && H > 0 && W > 0) ? (size_t)3 * B * C * H * W : 0;
+    return (B > 0 && C > 0 && H > 0 && W > 0) ? array_layout<float>(nullptr, (size_t)3 * B * C * H * W).bytes / sizeof(float) : 0;
 }
 
 extern "C" int wmd_ssim_bwd(const float* x, const float* y, const float* g, float* dx, float* dy, int B, int C, int H, int W, int mode,
@@ -138,7 +139,8 @@ extern "C" int wmd_ssim_bwd(const float* x, const float* y, const float* g, floa
     if (st) return st;
     if (!g || (!dx && !dy)) return fail(WMD_ERR_BAD_ARG, "wmd_ssim_bwd: null gradient pointer");
     const size_t n = (size_t)B * C * H * W;
-    if (!workspace || workspace_floats < 3 * n) return fail(WMD_ERR_WORKSPACE, "wmd_ssim_bwd: workspace %zu < %zu floats", workspace_floats, 3 * n);
+    if ((st = check_workspace_floats("wmd_ssim_bwd", workspace, workspace_floats, wmd_ssim_bwd_workspace_floats(B, C, H, W)))) return st;
+    float* coef = array_layout<float>(workspace, 3 * n).p;
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
     // SSIM is symmetric in its two images: the gradient w.r.t. y is the same computation with the operands swapped
@@ -149,12 +151,12 @@ extern "C" int wmd_ssim_bwd(const float* x, const float* y, const float* g, floa
         const float* b = side == 0 ? y : x;
         {
             ProfScope prof("ssim_bwd_coef_kernel", 90.0 * n, 4.0 * 6.0 * n, s);
-            hipLaunchKernelGGL(ssim_bwd_coef_kernel, dim3(blocks), dim3(256), 0, s, a, b, g, workspace, B, C, H, W, mode, w_ssim);
+            hipLaunchKernelGGL(ssim_bwd_coef_kernel, dim3(blocks), dim3(256), 0, s, a, b, g, coef, B, C, H, W, mode, w_ssim);
         }
         st = check_launch("ssim_bwd_coef_kernel");
         if (st) return st;
         ProfScope prof("ssim_bwd_gather_kernel", 100.0 * n, 4.0 * 7.0 * n, s);
-        hipLaunchKernelGGL(ssim_bwd_gather_kernel, dim3(blocks), dim3(256), 0, s, a, b, g, workspace, d, B, C, H, W, mode, w_l1);
+        hipLaunchKernelGGL(ssim_bwd_gather_kernel, dim3(blocks), dim3(256), 0, s, a, b, g, coef, d, B, C, H, W, mode, w_l1);
         st = check_launch("ssim_bwd_gather_kernel");
         if (st) return st;
     }
@@ -360,7 +362,7 @@ extern "C" int wmd_warp_fwd(const wmd_warp_args* g, float* out, void* stream) {
 }
 
 extern "C" size_t wmd_warp_bwd_workspace_floats(const wmd_warp_args* g) {
-    return g ? (size_t)g->B * warp_blocks(g->H * g->W) * 12 : 0;
+    return g ? array_layout<float>(nullptr, (size_t)g->B * warp_blocks(g->H * g->W) * 12).bytes / sizeof(float) : 0;
 }
 
 extern "C" int wmd_warp_bwd(const wmd_warp_args* g, const float* grad_out, float* ddepth, float* dT, float* workspace,
@@ -369,25 +371,25 @@ extern "C" int wmd_warp_bwd(const wmd_warp_args* g, const float* grad_out, float
     if (st) return st;
     if (!grad_out || !ddepth || !dT) return fail(WMD_ERR_BAD_ARG, "wmd_warp_bwd: null gradient pointer");
     const int nblk = warp_blocks(g->H * g->W);
-    if (!workspace || workspace_floats < (size_t)g->B * nblk * 12)
-        return fail(WMD_ERR_WORKSPACE, "wmd_warp_bwd: workspace %zu < %zu floats", workspace_floats, (size_t)g->B * nblk * 12);
+    if ((st = check_workspace_floats("wmd_warp_bwd", workspace, workspace_floats, wmd_warp_bwd_workspace_floats(g)))) return st;
+    float* partial = array_layout<float>(workspace, (size_t)g->B * nblk * 12).p;
     hipStream_t s = (hipStream_t)stream;
     const double n = (double)g->B * g->H * g->W;
     {
         ProfScope prof("warp_bwd_kernel", n * (120.0 + 14.0 * g->C), 4.0 * n * (2.0 + 2.0 * g->C), s);
         hipLaunchKernelGGL(warp_bwd_kernel, dim3(nblk, g->B), dim3(256), 0, s, g->src, g->depth, g->K, g->inv_K, g->T, grad_out, ddepth,
-                           workspace, g->B, g->C, g->H, g->W, g->Hs, g->Ws, g->eps);
+                           partial, g->B, g->C, g->H, g->W, g->Hs, g->Ws, g->eps);
     }
     st = check_launch("warp_bwd_kernel");
     if (st) return st;
-    hipLaunchKernelGGL(warp_bwd_finish_kernel, dim3(g->B), dim3(64), 0, s, workspace, g->K, dT, g->B, nblk);
+    hipLaunchKernelGGL(warp_bwd_finish_kernel, dim3(g->B), dim3(64), 0, s, partial, g->K, dT, g->B, nblk);
     return check_launch("warp_bwd_finish_kernel");
 }
 
 static int smooth_blocks(int total) { return std::max(1, std::min((total + 2047) / 2048, 512)); }
 
 extern "C" size_t wmd_smooth_workspace_floats(int B, int H, int W) {
-    return (B > 0 && H > 0 && W > 0) ? (size_t)smooth_blocks(B * H * W) * 2 * 2 + 2 : 0;   // fp64 partials (+ alignment slack)
+    return (B > 0 && H > 0 && W > 0) ? array_layout<double>(nullptr, (size_t)smooth_blocks(B * H * W) * 2, alignof(float)).bytes / sizeof(float) : 0;
 }
 
 extern "C" int wmd_smooth_fwd(const float* disp, const float* img, float* out, int B, int C, int H, int W, float gamma, float* workspace,
@@ -395,11 +397,10 @@ extern "C" int wmd_smooth_fwd(const float* disp, const float* img, float* out, i
     if (!disp || !img || !out) return fail(WMD_ERR_BAD_ARG, "wmd_smooth_fwd: null tensor pointer");
     if (B <= 0 || C <= 0 || H < 2 || W < 2) return fail(WMD_ERR_BAD_SHAPE, "wmd_smooth_fwd: B=%d C=%d H=%d W=%d", B, C, H, W);
     if ((double)B * C * H * W > 2147483647.0) return fail(WMD_ERR_UNSUPPORTED, "wmd_smooth_fwd: more than 2^31 elements");
-    if (!workspace || workspace_floats < wmd_smooth_workspace_floats(B, H, W))
-        return fail(WMD_ERR_WORKSPACE, "wmd_smooth_fwd: workspace %zu < %zu floats", workspace_floats, wmd_smooth_workspace_floats(B, H, W));
+    if (int st = check_workspace_floats("wmd_smooth_fwd", workspace, workspace_floats, wmd_smooth_workspace_floats(B, H, W))) return st;
     hipStream_t s = (hipStream_t)stream;
     const int nblk = smooth_blocks(B * H * W);
-    double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + 7) & ~(uintptr_t)7);
+    double* partial = array_layout<double>(workspace, (size_t)nblk * 2, alignof(float)).p;
     const double n = (double)B * H * W;
     ProfScope prof("smooth_fwd_kernel", n * (8.0 + 6.0 * C), 4.0 * n * (1.0 + C), s);
     hipLaunchKernelGGL(smooth_fwd_kernel, dim3(nblk), dim3(256), 0, s, disp, img, partial, B, C, H, W, gamma);

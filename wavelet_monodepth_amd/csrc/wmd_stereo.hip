@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <stdint.h>
 #include "wmd_internal.h"
+#include "wmd_ws_layouts.h"
 
 namespace wmd {
 
@@ -400,13 +401,11 @@ __global__ __launch_bounds__(256) void speckle_clear_kernel(int16_t* __restrict_
     if (counts[uf_find(labels, i)] <= max_size) disp[i] = (int16_t)invalid;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// n = images * H * W pixels of `disp`; workspace: 2 n ints
+// n = images * H * W pixels of `disp`; workspace: speckle_layout(n)
 static int speckle_launch(int16_t* disp, int images, int H, int W, int invalid, int max_size, int max_diff, void* workspace, hipStream_t s) {
     const int n = images * H * W, blocks = (n + 255) / 256;
-    int* labels = (int*)workspace;
-    int* counts = labels + n;
+    const SpeckleWs ws = speckle_layout(workspace, n);
+    int *labels = ws.labels, *counts = ws.counts;
     const double px = (double)n;
     {
         ProfScope prof("speckle_init_kernel", px, 10.0 * px, s);
@@ -430,9 +429,8 @@ static int speckle_launch(int16_t* disp, int images, int H, int W, int invalid, 
 // ---------------------------------------------------------------- host side
 struct StereoPlan {
     int Wv, r, TY, group;
-    size_t volume;                                    // elements of one image's cost volume (and of S)
-    size_t prep_b, vol_b, keys_b, map_b, speckle_b;   // bytes per image, each a multiple of 256
-    size_t per_image() const { return prep_b + 2 * vol_b + keys_b + map_b + speckle_b; }
+    size_t volume;   // elements of one image's cost volume (and of S)
+    size_t bytes;    // stereo_layout of `group` images
 };
 
 // the checks that need no pointer; 0 = fine
@@ -453,12 +451,8 @@ static int stereo_check(const char* who, int B, int H, int W, int C, int min_dis
         if (cost_tile(ty, p.r, C, num_disp).bytes <= kCostLdsMax) p.TY = ty;
     if (!p.TY) return fail(WMD_ERR_UNSUPPORTED, "%s: a blockSize=%d window over %d disparities does not fit the cost kernel's LDS tile", who, block, num_disp);
     p.volume = (size_t)vol;
-    p.prep_b = align256((size_t)2 * H * W * C * sizeof(uint2));
-    p.vol_b = align256(p.volume * sizeof(uint16_t));
-    p.keys_b = align256((size_t)H * W * sizeof(unsigned));
-    p.map_b = align256((size_t)H * W * sizeof(int16_t));
-    p.speckle_b = align256((size_t)H * W * 2 * sizeof(int));
-    p.group = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, kStereoGroupCap / p.per_image()));
+    p.group = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, kStereoGroupCap / stereo_layout(nullptr, 1, H, W, C, p.volume).bytes));
+    p.bytes = stereo_layout(nullptr, p.group, H, W, C, p.volume).bytes;
     if (plan) *plan = p;
     return WMD_OK;
 }
@@ -482,24 +476,24 @@ using namespace wmd;
 extern "C" size_t wmd_stereo_sgbm_workspace_bytes(int B, int H, int W, int C, int min_disp, int num_disp, int block) {
     StereoPlan p;
     if (stereo_check("wmd_stereo_sgbm_workspace_bytes", B, H, W, C, min_disp, num_disp, block, &p) != WMD_OK) return 0;
-    return p.per_image() * p.group;
+    return p.bytes;
 }
 
 extern "C" size_t wmd_stereo_filter_speckles_workspace_bytes(int B, int H, int W) {
     if (B < 1 || H < 1 || W < 1 || (double)B * H * W > 2147483647.0) return 0;
-    return align256((size_t)B * H * W * 2 * sizeof(int));
+    return speckle_layout(nullptr, (size_t)B * H * W).bytes;
 }
 
 extern "C" int wmd_stereo_filter_speckles(short* disp, int B, int H, int W, int invalid, int max_size, int max_diff, void* workspace,
                                           size_t workspace_bytes, void* stream) {
     const char* who = "wmd_stereo_filter_speckles";
-    if (!disp || !workspace) return fail(WMD_ERR_BAD_ARG, "%s: null pointer", who);
+    if (!disp || !workspace) return fail(WMD_ERR_BAD_ARG, "%s: null pointer (disp or workspace)", who);
     if (B < 1 || H < 1 || W < 1) return fail(WMD_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d", who, B, H, W);
     if (max_size < 0 || max_diff < 0 || invalid < -32768 || invalid > 32767)
         return fail(WMD_ERR_BAD_ARG, "%s: max_size=%d max_diff=%d invalid=%d", who, max_size, max_diff, invalid);
     const size_t need = wmd_stereo_filter_speckles_workspace_bytes(B, H, W);
     if (!need) return fail(WMD_ERR_UNSUPPORTED, "%s: more than 2^31 pixels", who);
-    if (workspace_bytes < need || ((uintptr_t)workspace & 3)) return fail(WMD_ERR_WORKSPACE, "%s: workspace %zu bytes at %p, %zu needed, 4-byte aligned", who, workspace_bytes, workspace, need);
+    if (int st = check_workspace(who, workspace, workspace_bytes, need, 4, WMD_ERR_WORKSPACE)) return st;
     return speckle_launch((int16_t*)disp, B, H, W, invalid, max_size, max_diff, workspace, (hipStream_t)stream);
 }
 
@@ -508,7 +502,7 @@ extern "C" int wmd_stereo_sgbm(const unsigned char* left, const unsigned char* r
                                int block, int P1, int P2, int cap, int uniq, int speckle_win, int speckle_range, int disp12,
                                int directions, void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "wmd_stereo_sgbm";
-    if (!left || !right || !disp || !workspace) return fail(WMD_ERR_BAD_ARG, "%s: null pointer", who);
+    if (!left || !right || !disp || !workspace) return fail(WMD_ERR_BAD_ARG, "%s: null pointer (left, right, disp or workspace)", who);
     StereoPlan p;
     const int st = stereo_check(who, B, H, W, C, min_disp, num_disp, block, &p);
     if (st != WMD_OK) return st;
@@ -521,40 +515,29 @@ extern "C" int wmd_stereo_sgbm(const unsigned char* left, const unsigned char* r
     const double bound = (double)directions * ((double)win * win * C * (2 * cap + 63) + P2);
     if (bound > 65535.0) return fail(WMD_ERR_UNSUPPORTED, "%s: S can reach %.0f with these settings, the volumes hold 16 bits", who, bound);
     if (speckle_range > 2047) return fail(WMD_ERR_UNSUPPORTED, "%s: speckleRange=%d", who, speckle_range);
-    const size_t need = p.per_image() * p.group;
-    if (workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(WMD_ERR_WORKSPACE, "%s: workspace %zu bytes at %p, %zu needed, 256-byte aligned", who, workspace_bytes, workspace, need);
+    if (int st2 = check_workspace(who, workspace, workspace_bytes, p.bytes, 256, WMD_ERR_WORKSPACE)) return st2;
 
     hipStream_t s = (hipStream_t)stream;
     const int D = num_disp, Wv = p.Wv, NR = (D + 63) / 64, tol = disp12 > 0 ? disp12 : 1, invalid = (min_disp - 1) * 16;
-    char* ws = (char*)workspace;
-    uint2* prep = (uint2*)ws;
-    ws += p.prep_b * p.group;
-    uint16_t* ws_cost = (uint16_t*)ws;
-    ws += p.vol_b * p.group;
-    uint16_t* ws_S = (uint16_t*)ws;
-    ws += p.vol_b * p.group;
-    unsigned* keys = (unsigned*)ws;
-    ws += p.keys_b * p.group;
-    int16_t* first_map = (int16_t*)ws;
-    ws += p.map_b * p.group;
-    void* speckle_ws = ws;
+    const StereoWs ws = stereo_layout(workspace, p.group, H, W, C, p.volume);
+    const size_t vol_stride = stereo_stride<uint16_t>(p.volume);
     static const int steps[8][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {-1, 0}, {-1, -1}, {0, -1}, {1, -1}};   // minus the predecessor offsets
     const CostTile tile = cost_tile(p.TY, p.r, C, D);
 
     for (int b0 = 0; b0 < B; b0 += p.group) {
         const int G = std::min(p.group, B - b0);
-        // a caller's volume is [B][H][Wv][D] dense; the workspace's images sit vol_b apart
-        uint16_t* cost = cost_out ? cost_out + (size_t)b0 * p.volume : ws_cost;
-        uint16_t* S = S_out ? S_out + (size_t)b0 * p.volume : ws_S;
-        const size_t cstride = cost_out ? p.volume : p.vol_b / sizeof(uint16_t), sstride = S_out ? p.volume : p.vol_b / sizeof(uint16_t);
+        // a caller's volume is [B][H][Wv][D] dense; the workspace's images sit vol_stride apart
+        uint16_t* cost = cost_out ? cost_out + (size_t)b0 * p.volume : ws.cost;
+        uint16_t* S = S_out ? S_out + (size_t)b0 * p.volume : ws.S;
+        const size_t cstride = cost_out ? p.volume : vol_stride, sstride = S_out ? p.volume : vol_stride;
         const double px = (double)G * H * W, vol = (double)G * p.volume;
         {
             ProfScope prof("stereo_prep_kernel", 60.0 * px * C * 2, px * C * 2 * (9.0 + 8.0), s);
-            hipLaunchKernelGGL(stereo_prep_kernel, dim3((W * C + 255) / 256, H, 2 * G), dim3(256), 0, s, left, right, reverse, prep, b0, H, W, C, cap);
+            hipLaunchKernelGGL(stereo_prep_kernel, dim3((W * C + 255) / 256, H, 2 * G), dim3(256), 0, s, left, right, reverse, ws.prep, b0, H, W, C, cap);
         }
         {
             ProfScope prof("stereo_cost_kernel", vol * (20.0 * C * tile.rows * tile.LW / (p.TY * kCostTX) + win * win), 2.0 * vol + 16.0 * px * C, s);
-            hipLaunchKernelGGL(stereo_cost_kernel, dim3((Wv + kCostTX - 1) / kCostTX, (H + p.TY - 1) / p.TY, G), dim3(kCostThreads), tile.bytes, s, prep, cost,
+            hipLaunchKernelGGL(stereo_cost_kernel, dim3((Wv + kCostTX - 1) / kCostTX, (H + p.TY - 1) / p.TY, G), dim3(kCostThreads), tile.bytes, s, ws.prep, cost,
                                H, W, C, min_disp, D, p.r, p.TY, cstride);
         }
         for (int k = 0; k < directions; ++k) {
@@ -581,25 +564,25 @@ extern "C" int wmd_stereo_sgbm(const unsigned char* left, const unsigned char* r
                 }
             }
         }
-        if (hipMemsetAsync(keys, 0xFF, (size_t)G * H * W * sizeof(unsigned), s) != hipSuccess) return check_launch("stereo keys memset");
+        if (hipMemsetAsync(ws.keys, 0xFF, (size_t)G * H * W * sizeof(unsigned), s) != hipSuccess) return check_launch("stereo keys memset");
         {
             ProfScope prof("stereo_winner_kernel", 6.0 * vol, 2.0 * vol + 10.0 * px, s);
             switch (NR) {
-                case 1: winner_launch<1>(S, first_map, keys, G, H, W, min_disp, D, uniq, sstride, s); break;
-                case 2: winner_launch<2>(S, first_map, keys, G, H, W, min_disp, D, uniq, sstride, s); break;
-                case 3: winner_launch<3>(S, first_map, keys, G, H, W, min_disp, D, uniq, sstride, s); break;
-                default: winner_launch<4>(S, first_map, keys, G, H, W, min_disp, D, uniq, sstride, s); break;
+                case 1: winner_launch<1>(S, ws.first_map, ws.keys, G, H, W, min_disp, D, uniq, sstride, s); break;
+                case 2: winner_launch<2>(S, ws.first_map, ws.keys, G, H, W, min_disp, D, uniq, sstride, s); break;
+                case 3: winner_launch<3>(S, ws.first_map, ws.keys, G, H, W, min_disp, D, uniq, sstride, s); break;
+                default: winner_launch<4>(S, ws.first_map, ws.keys, G, H, W, min_disp, D, uniq, sstride, s); break;
             }
         }
         {
             ProfScope prof("stereo_finish_kernel", 10.0 * px, 12.0 * px, s);
-            hipLaunchKernelGGL(stereo_finish_kernel, dim3((W + 255) / 256, H, G), dim3(256), 0, s, first_map, keys, reverse, (int16_t*)disp, b0, H, W, min_disp,
+            hipLaunchKernelGGL(stereo_finish_kernel, dim3((W + 255) / 256, H, G), dim3(256), 0, s, ws.first_map, ws.keys, reverse, (int16_t*)disp, b0, H, W, min_disp,
                                D, tol);
         }
         const int st2 = check_launch("stereo kernels");
         if (st2 != WMD_OK) return st2;
         if (speckle_win > 0) {
-            const int st3 = speckle_launch((int16_t*)disp + (size_t)b0 * H * W, G, H, W, invalid, speckle_win, 16 * speckle_range, speckle_ws, s);
+            const int st3 = speckle_launch((int16_t*)disp + (size_t)b0 * H * W, G, H, W, invalid, speckle_win, 16 * speckle_range, ws.speckle, s);
             if (st3 != WMD_OK) return st3;
         }
     }

@@ -17,6 +17,7 @@
 #include <cstdint>
 #include "wmd_internal.h"
 #include "wmd_select.h"
+#include "wmd_ws_layouts.h"
 
 // numpy and matplotlib round every operation on its own: no fused multiply-add may be formed from their products.  The
 // pragma covers what the front end would fuse; the library is built with the HIP default, under which the back end still
@@ -189,7 +190,7 @@ static int vz_blocks(size_t plane, int B, size_t per_block) {
     return (int)std::max<size_t>(1, std::min(want, cap));
 }
 
-static size_t vz_state_bytes(int B) { return (size_t)B * VZ_STATE * sizeof(unsigned); }
+static size_t vz_state_bytes(int B) { return viz_layout(nullptr, B, 0).bytes; }
 
 }  // namespace wmd
 
@@ -197,24 +198,22 @@ using namespace wmd;
 
 extern "C" size_t wmd_viz_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    // [B] selection states (min, the key above the prefix, max, three histograms), then one resized plane per image
-    return vz_state_bytes(B) + (size_t)B * H * W * sizeof(float);
+    return viz_layout(nullptr, B, (size_t)H * W).bytes;
 }
 
 extern "C" int wmd_viz_disparity(const float* disp, int B, int h, int w, int H, int W, double percentile, const unsigned char* lut,
                                  unsigned char* rgb, float* resized, float* range, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-    if (!disp || !lut || !rgb || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_viz_disparity: null pointer");
+    if (!disp || !lut || !rgb || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_viz_disparity: null pointer (disp, lut, rgb or workspace)");
     if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
         return fail(WMD_ERR_BAD_SHAPE, "wmd_viz_disparity: B=%d h=%d w=%d H=%d W=%d", B, h, w, H, W);
     if (!(percentile >= 0.0 && percentile <= 100.0)) return fail(WMD_ERR_BAD_ARG, "wmd_viz_disparity: percentile %g outside [0, 100]", percentile);
     if ((double)H * W > 2147483647.0) return fail(WMD_ERR_UNSUPPORTED, "wmd_viz_disparity: more than 2^31 pixels per image");
     if (B > 65535) return fail(WMD_ERR_UNSUPPORTED, "wmd_viz_disparity: B=%d above 65535", B);
-    if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(WMD_ERR_BAD_ARG, "wmd_viz_disparity: workspace not 4-byte aligned");
-    const size_t need = wmd_viz_workspace_bytes(B, H, W);
-    if (workspace_bytes < need) return fail(WMD_ERR_WORKSPACE, "wmd_viz_disparity: workspace %zu < %zu bytes", workspace_bytes, need);
-    hipStream_t s = (hipStream_t)stream;
     const size_t plane = (size_t)H * W;
+    if (int st = check_workspace("wmd_viz_disparity", workspace, workspace_bytes, wmd_viz_workspace_bytes(B, H, W), 4, WMD_ERR_BAD_ARG)) return st;
+    const VizWs ws = viz_layout(workspace, B, plane);
+    hipStream_t s = (hipStream_t)stream;
     // numpy's virtual index of the "linear" method on a float32 array, in float32
     const float qf = (float)percentile / 100.0f;
     const volatile float vi_rounded = (float)(plane - 1) * qf;   // the product, rounded, before the floor is taken off it
@@ -223,10 +222,10 @@ extern "C" int wmd_viz_disparity(const float* disp, int B, int h, int w, int H, 
     const float g = vi - kf;
     const unsigned last = (unsigned)(plane - 1);
     const unsigned rank = std::min((unsigned)kf, last), rank_next = std::min(rank + 1, last);
-    unsigned* state = reinterpret_cast<unsigned*>(workspace);
+    unsigned* state = ws.state;
     const float* map = disp;
     if (h != H || w != W) {
-        float* dst = resized ? resized : reinterpret_cast<float*>(state + (size_t)B * VZ_STATE);
+        float* dst = resized ? resized : ws.resized;
         const int st = wmd_upsample_bilinear_fwd(disp, dst, nullptr, B, h, w, H, W, 0, 0.f, 0.f, stream);
         if (st) return st;
         map = dst;
@@ -264,12 +263,11 @@ extern "C" int wmd_viz_colorize(const float* x, int B, size_t n, int auto_range,
     if (B <= 0 || n == 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_viz_colorize: B=%d n=%zu", B, n);
     if (B > 65535) return fail(WMD_ERR_UNSUPPORTED, "wmd_viz_colorize: B=%d above 65535", B);
     hipStream_t s = (hipStream_t)stream;
-    unsigned* state = reinterpret_cast<unsigned*>(workspace);
+    unsigned* state = nullptr;   // stays null with a given range: the colour kernel does not read it then
     if (auto_range) {
         if (!workspace) return fail(WMD_ERR_BAD_ARG, "wmd_viz_colorize: null workspace");
-        if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(WMD_ERR_BAD_ARG, "wmd_viz_colorize: workspace not 4-byte aligned");
-        if (workspace_bytes < vz_state_bytes(B))
-            return fail(WMD_ERR_WORKSPACE, "wmd_viz_colorize: workspace %zu < %zu bytes", workspace_bytes, vz_state_bytes(B));
+        if (int st = check_workspace("wmd_viz_colorize", workspace, workspace_bytes, vz_state_bytes(B), 4, WMD_ERR_BAD_ARG)) return st;
+        state = viz_layout(workspace, B, 0).state;
         if (hipMemsetAsync(state, 0, vz_state_bytes(B), s) != hipSuccess) return fail(WMD_ERR_HIP, "wmd_viz_colorize: hipMemsetAsync failed");
         ProfScope prof("viz_minmax_kernel", 0.0, 4.0 * B * n, s);
         hipLaunchKernelGGL(viz_minmax_kernel, dim3(vz_blocks(n, B, 4096), B), dim3(VZ_THREADS), 0, s, x, state, n);
@@ -287,14 +285,12 @@ extern "C" int wmd_viz_colorize(const float* x, int B, size_t n, int auto_range,
 }
 
 extern "C" int wmd_viz_normalize(const float* x, float* y, int B, size_t n, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !y || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_viz_normalize: null pointer");
+    if (!x || !y || !workspace) return fail(WMD_ERR_BAD_ARG, "wmd_viz_normalize: null pointer (x, y or workspace)");
     if (B <= 0 || n == 0) return fail(WMD_ERR_BAD_SHAPE, "wmd_viz_normalize: B=%d n=%zu", B, n);
     if (B > 65535) return fail(WMD_ERR_UNSUPPORTED, "wmd_viz_normalize: B=%d above 65535", B);
-    if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(WMD_ERR_BAD_ARG, "wmd_viz_normalize: workspace not 4-byte aligned");
-    if (workspace_bytes < vz_state_bytes(B))
-        return fail(WMD_ERR_WORKSPACE, "wmd_viz_normalize: workspace %zu < %zu bytes", workspace_bytes, vz_state_bytes(B));
+    if (int st = check_workspace("wmd_viz_normalize", workspace, workspace_bytes, vz_state_bytes(B), 4, WMD_ERR_BAD_ARG)) return st;
     hipStream_t s = (hipStream_t)stream;
-    unsigned* state = reinterpret_cast<unsigned*>(workspace);
+    unsigned* state = viz_layout(workspace, B, 0).state;
     if (hipMemsetAsync(state, 0, vz_state_bytes(B), s) != hipSuccess) return fail(WMD_ERR_HIP, "wmd_viz_normalize: hipMemsetAsync failed");
     const int nblk = vz_blocks(n, B, 4096);
     {

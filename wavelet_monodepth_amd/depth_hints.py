@@ -17,18 +17,10 @@ from ._lib import check, current_stream, ptr
 MAX_CANDIDATES = 64   # WMD_DEPTH_HINTS_MAX_CANDIDATES
 
 
-def _gpu(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.WmdError("the depth-hint operators run on the GPU only (got a %s tensor)" % t.device)
-        if t.dtype != torch.float32:
-            raise _lib.WmdError("float32 tensors expected (got %s)" % t.dtype)
-
-
 def disparity_to_depth(disps, focal, baseline=0.1):
     """Pixel disparities -> depths, "ignoring missing pixels": focal * baseline / (d + 1e-7) * (d > 0).  `focal` is K[0, 0]
     in pixels of the map's width."""
-    _gpu(disps)
+    _lib.require_device("disparity_to_depth", disps=(disps, torch.float32))
     fb = (torch.tensor(float(focal), dtype=torch.float32) * baseline).to(disps.device)   # a float32 product, as in the reference
     return fb / (disps + 1e-7) * (disps > 0).float()   # tensor / tensor: a true division (scalar / tensor multiplies by a reciprocal)
 
@@ -44,7 +36,8 @@ def fuse_depth_hints(candidates, base_image, lookup_image, K, inv_K, T, *, dispa
     single = candidates.dim() == 3
     if single:
         candidates, base_image, lookup_image, K, inv_K, T = (t.unsqueeze(0) for t in (candidates, base_image, lookup_image, K, inv_K, T))
-    _gpu(candidates, base_image, lookup_image, K, inv_K, T)
+    _lib.require_device("fuse_depth_hints", **{k: (v, torch.float32) for k, v in (("candidates", candidates), ("base_image", base_image),
+                                                                                   ("lookup_image", lookup_image), ("K", K), ("inv_K", inv_K), ("T", T))})
     if candidates.dim() != 4 or base_image.dim() != 4:
         raise _lib.WmdError("candidates must be [B,M,H,W] or [M,H,W] and the images [B,C,H,W] or [C,H,W]")
     B, M, H, W = candidates.shape
@@ -63,7 +56,7 @@ def fuse_depth_hints(candidates, base_image, lookup_image, K, inv_K, T, *, dispa
     losses = torch.empty((B, M, H, W), device=dev, dtype=torch.float32) if return_losses else None
     l = _lib.lib()
     n = l.wmd_depth_hints_workspace_floats(B, M, H, W)
-    ws = torch.empty(n, device=dev, dtype=torch.float32) if n else None
+    ws = _lib.float_workspace(n, dev)
     w_ssim, w_l1 = (0.0, 1.0) if no_ssim else (0.85, 0.15)
     check(l.wmd_depth_hints_fuse(ptr(cand), 1 if disparities else 0, float(focal_times_baseline or 0.0), ptr(base), ptr(look), ptr(K),
                                  ptr(inv_K), ptr(T), ptr(best_depth), ptr(best_index), ptr(losses), B, M, Cc, H, W, 1e-7, w_ssim, w_l1,

@@ -25,20 +25,12 @@ NYU_EDGE_NAMES = ("dbe_acc", "dbe_com")
 MIN_DEPTH, MAX_DEPTH, STEREO_SCALE_FACTOR = 1e-3, 80.0, 5.4
 
 
-def _gpu(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise _lib.WmdError("evaluation runs on the GPU only (got a %s tensor)" % t.device)
-        if t.dtype != torch.float32:
-            raise _lib.WmdError("evaluation expects float32 tensors (got %s)" % t.dtype)
-
-
 def kitti_metrics(pred_disp, gt_depth, eval_split="eigen", eval_stereo=False, disable_median_scaling=False,
                   pred_depth_scale_factor=1.0, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH):
     """pred_disp [B,h,w] (network resolution), gt_depth [B,H,W] -> (errors [B,7] in KITTI_NAMES order, ratios [B] or
     None, n_valid [B]).  Options follow evaluate_depth.py:263-270: stereo evaluation disables median scaling and scales
     by 5.4."""
-    _gpu(pred_disp, gt_depth)
+    _lib.require_device("kitti_metrics", pred_disp=(pred_disp, torch.float32), gt_depth=(gt_depth, torch.float32))
     if eval_stereo:
         disable_median_scaling, pred_depth_scale_factor = True, STEREO_SCALE_FACTOR
     l = _lib.lib()
@@ -48,7 +40,7 @@ def kitti_metrics(pred_disp, gt_depth, eval_split="eigen", eval_stereo=False, di
     if B != Bg:
         raise _lib.WmdError("batch mismatch: %d predictions, %d ground-truth maps" % (B, Bg))
     n = l.wmd_eval_workspace_floats(B, H, W)
-    ws = torch.empty(n, device=pred_disp.device, dtype=torch.float32)
+    ws = _lib.float_workspace(n, pred_disp.device)
     out = torch.empty((B, 9), device=pred_disp.device, dtype=torch.float32)
     a = _lib.EvalKittiArgs(B=B, h=h, w=w, H=H, W=W, min_depth=float(min_depth), max_depth=float(max_depth),
                            mask_mode=1 if eval_split == "eigen" else 0, pred_scale=float(pred_depth_scale_factor),
@@ -63,7 +55,7 @@ def kitti_metrics(pred_disp, gt_depth, eval_split="eigen", eval_stereo=False, di
 
 
 def _errors9(pred, gt):
-    _gpu(pred, gt)
+    _lib.require_device("compute_errors", pred=(pred, torch.float32), gt=(gt, torch.float32))
     if pred.shape != gt.shape:
         raise _lib.WmdError("shape mismatch %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
     pred, gt = pred.contiguous(), gt.contiguous()
@@ -93,7 +85,7 @@ def compute_errors_nyu(pred, gt, per_image=False):
 
 def flip_postprocess(l_disp, r_disp_raw):
     """Monodepth-v1 post-processing; r_disp_raw is the prediction for the mirrored image, not flipped back."""
-    _gpu(l_disp, r_disp_raw)
+    _lib.require_device("flip_postprocess", l_disp=(l_disp, torch.float32), r_disp_raw=(r_disp_raw, torch.float32))
     l_disp, r_disp_raw = l_disp.contiguous(), r_disp_raw.contiguous()
     B, h, w = l_disp.shape
     out = torch.empty_like(l_disp)
@@ -103,7 +95,7 @@ def flip_postprocess(l_disp, r_disp_raw):
 
 def nyu_prediction(pred_y, crop, border_crop_size=16):
     """NYUv2/utils.py:213-226,247-250 on the GPU: pred_y [B,1,H,W] (already / 100) -> [B, crop rows, crop cols]."""
-    _gpu(pred_y)
+    _lib.require_device("nyu_prediction", pred_y=(pred_y, torch.float32))
     t = ops.upsample_bilinear(pred_y, (240 - border_crop_size, 320 - border_crop_size), align_corners=True)
     t = torch.nn.functional.pad(t, (border_crop_size // 2,) * 4, mode="replicate")
     t = ops.upsample_bilinear(t, (2 * t.shape[2], 2 * t.shape[3]), align_corners=True)
@@ -111,15 +103,9 @@ def nyu_prediction(pred_y, crop, border_crop_size=16):
     return t[:, 0, crop[0]:crop[1] + 1, crop[2]:crop[3] + 1]
 
 
-def _edge_args(B, H, W, dev):
-    n = _lib.lib().wmd_eval_dbe_workspace_bytes(B, H, W)
-    return torch.empty(max(n, 8) // 8 + 1, device=dev, dtype=torch.float64), n
-
-
 def _u8(t, what, shape):
     """bool / uint8 / float map, nonzero = set -> contiguous uint8 of 0 / 1"""
-    if not t.is_cuda:
-        raise _lib.WmdError("evaluation runs on the GPU only (got a %s tensor)" % t.device)
+    _lib.require_device("compute_depth_boundary_error", **{what: (t, None)})   # any dtype: nonzero = set
     if tuple(t.shape) != tuple(shape):
         raise _lib.WmdError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
     return (t != 0).to(torch.uint8).contiguous()
@@ -131,7 +117,7 @@ def canny(image, sigma=1.0, low_threshold=0.1, high_threshold=0.2):
     8-connected components; thresholds are absolute, all arithmetic float64, NaN pixels spread and never become edges.
     Modelled on skimage.feature.canny(image, sigma, low_threshold, high_threshold) with mask=None; skimage was not at hand
     when this was written, so the agreement is by construction only."""
-    _gpu(image)
+    _lib.require_device("canny", image=(image, torch.float32))
     img = image.contiguous()
     if img.dim() == 2:
         img = img[None]
@@ -139,7 +125,7 @@ def canny(image, sigma=1.0, low_threshold=0.1, high_threshold=0.2):
         raise _lib.WmdError("canny expects [B,H,W] or [H,W], got %s" % (tuple(image.shape),))
     B, H, W = img.shape
     edges = torch.empty((B, H, W), device=img.device, dtype=torch.uint8)
-    ws, n = _edge_args(B, H, W, img.device)
+    ws, n = _lib.byte_workspace(_lib.lib().wmd_eval_dbe_workspace_bytes(B, H, W), img.device)
     check(_lib.lib().wmd_eval_canny(ptr(img), ptr(edges), B, H, W, float(sigma), float(low_threshold), float(high_threshold),
                                     ptr(ws), n, current_stream()), "wmd_eval_canny")
     return edges.bool().view(image.shape)
@@ -154,7 +140,7 @@ def compute_depth_boundary_error(edges_gt, pred, mask=None, low_thresh=0.15, hig
     An image without ground-truth edges scores (nan, nan) with an empty edge map: the reference assigns those values and
     then fails on an unbound D_est in its return statement (:169).  Deterministic: the same input gives the same bits.
     The reference is called once per image on the host (NYUv2/utils.py:262-266); this is one call per batch."""
-    _gpu(pred)
+    _lib.require_device("compute_depth_boundary_error", pred=(pred, torch.float32))
     if pred.dim() != 3:
         raise _lib.WmdError("compute_depth_boundary_error expects pred [B,H,W], got %s" % (tuple(pred.shape),))
     pred = pred.contiguous()
@@ -163,7 +149,7 @@ def compute_depth_boundary_error(edges_gt, pred, mask=None, low_thresh=0.15, hig
     m = None if mask is None else _u8(mask, "mask", pred.shape)
     scores = torch.empty((B, 2), device=pred.device, dtype=torch.float32)
     edges = torch.empty((B, H, W), device=pred.device, dtype=torch.uint8)
-    ws, n = _edge_args(B, H, W, pred.device)
+    ws, n = _lib.byte_workspace(_lib.lib().wmd_eval_dbe_workspace_bytes(B, H, W), pred.device)
     check(_lib.lib().wmd_eval_dbe(ptr(pred), ptr(gt), ptr(m), ptr(scores), ptr(edges), B, H, W, float(low_thresh),
                                   float(high_thresh), ptr(ws), n, current_stream()), "wmd_eval_dbe")
     return scores, edges.bool()

@@ -19,14 +19,6 @@ from . import _lib, resample
 from ._lib import check, current_stream, ptr
 
 
-def _gpu(who, **ts):
-    for name, (t, dtypes) in ts.items():
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.WmdError("%s runs on the GPU only (%s is %s)" % (who, name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-        if t.dtype not in dtypes:
-            raise _lib.WmdError("%s: %s must be %s (got %s)" % (who, name, " or ".join(str(d) for d in dtypes), t.dtype))
-
-
 class ColorJitterParams:
     """Per item: enable uint8 [N]; order uint8 [N,4], a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue;
     factors float32 [N,3] for brightness, contrast, saturation; hue_shift int32 [N] in 0..255 (added to the 8-bit H).
@@ -66,7 +58,7 @@ class ColorJitterParams:
         return ColorJitterParams(*(t.repeat_interleave(k, dim=0) for t in (self.enable, self.order, self.factors, self.hue_shift)))
 
     def _checked(self, who, n, device):
-        _gpu(who, enable=(self.enable, (torch.uint8,)))
+        _lib.require_device(who, enable=(self.enable, torch.uint8))
         if len(self) != n or self.enable.device != device:
             raise _lib.WmdError("%s: jitter holds %d items on %s, the images are %d on %s" % (who, len(self), self.enable.device, n, device))
         return [ptr(t) for t in (self.enable, self.order, self.factors, self.hue_shift)]
@@ -95,14 +87,14 @@ def color_pyramid(frames, height, width, num_scales=4, flip=None, jitter=None):
     scale s, h = height // 2**s, w = width // 2**s.  flip: optional uint8 / bool [N]; jitter: optional ColorJitterParams of
     N items.  Without jitter color_aug is color itself."""
     who = "color_pyramid"
-    _gpu(who, frames=(frames, (torch.uint8,)))
+    _lib.require_device(who, frames=(frames, torch.uint8))
     if frames.dim() != 4 or frames.shape[3] != 3:
         raise _lib.WmdError("frames must be [N,H0,W0,3] (got %s)" % (tuple(frames.shape),))
     N, H0, W0 = (int(v) for v in frames.shape[:3])
     height, width, num_scales = int(height), int(width), int(num_scales)
     dev = frames.device
     if flip is not None:
-        _gpu(who, flip=(flip, (torch.uint8, torch.bool)))
+        _lib.require_device(who, flip=(flip, (torch.uint8, torch.bool)))
         if tuple(flip.shape) != (N,) or flip.device != dev:
             raise _lib.WmdError("flip must be [%d] on %s (got %s on %s)" % (N, dev, tuple(flip.shape), flip.device))
         flip = flip.to(torch.uint8).contiguous()
@@ -113,7 +105,7 @@ def color_pyramid(frames, height, width, num_scales=4, flip=None, jitter=None):
     pixels = sum(N * h * w for h, w in sizes) if n_ws else 0
     tables = resample.device_tables("color_pyramid", (H0, W0, height, width, num_scales), dev) if n_ws else torch.zeros(1, dtype=torch.int32, device=dev)
     frames = frames.contiguous()
-    ws = torch.empty(max(n_ws, 8) // 8, device=dev, dtype=torch.int64)
+    ws, _ = _lib.byte_workspace(n_ws, dev)
     levels = torch.empty(max(pixels, 1) * 3, device=dev, dtype=torch.uint8)
     color = torch.empty(max(pixels, 1) * 3, device=dev, dtype=torch.float32)
     aug = torch.empty_like(color) if jitter is not None else None
@@ -132,7 +124,7 @@ def color_jitter(images_u8, jitter):
     """uint8 [N,h,w,3] -> uint8 [N,h,w,3]: torchvision 0.8.2's ColorJitter on PIL images with the given parameters, every
     image on its own (the contrast mean is that image's)."""
     who = "color_jitter"
-    _gpu(who, images_u8=(images_u8, (torch.uint8,)))
+    _lib.require_device(who, images_u8=(images_u8, torch.uint8))
     if images_u8.dim() != 4 or images_u8.shape[3] != 3:
         raise _lib.WmdError("images_u8 must be [N,h,w,3] (got %s)" % (tuple(images_u8.shape),))
     if not isinstance(jitter, ColorJitterParams):
@@ -141,8 +133,7 @@ def color_jitter(images_u8, jitter):
     jit = jitter._checked(who, N, images_u8.device)
     images_u8 = images_u8.contiguous()
     l = _lib.lib()
-    n_ws = l.wmd_color_jitter_workspace_bytes(N, h, w)
-    ws = torch.empty(max(n_ws, 8) // 8, device=images_u8.device, dtype=torch.int64)
+    ws, n_ws = _lib.byte_workspace(l.wmd_color_jitter_workspace_bytes(N, h, w), images_u8.device)
     out = torch.empty_like(images_u8)
     check(l.wmd_color_jitter(ptr(images_u8), ptr(out), N, h, w, jit[0], jit[1], jit[2], jit[3], ptr(ws), n_ws, current_stream()), "wmd_color_jitter")
     return out
@@ -161,13 +152,13 @@ def preprocess(frames_by_id, height, width, scales=range(4), do_flip=None, jitte
     first = frames_by_id[ids[0]]
     for f in ids:
         t = frames_by_id[f]
-        _gpu("preprocess", **{"frames[%r]" % (f,): (t, (torch.uint8,))})
+        _lib.require_device("preprocess", **{"frames[%r]" % (f,): (t, torch.uint8)})
         if t.shape != first.shape or t.device != first.device or t.dim() != 4:
             raise _lib.WmdError("preprocess: every frame must be uint8 [B,H0,W0,3] of one shape on one device")
     B, F = first.shape[0], len(ids)
     stacked = torch.stack([frames_by_id[f] for f in ids], dim=1).reshape((B * F,) + tuple(first.shape[1:]))
     if do_flip is not None:
-        _gpu("preprocess", do_flip=(do_flip, (torch.uint8, torch.bool)))
+        _lib.require_device("preprocess", do_flip=(do_flip, (torch.uint8, torch.bool)))
         do_flip = do_flip.repeat_interleave(F)
     if jitter is not None:
         jitter = jitter.repeat_interleave(F)

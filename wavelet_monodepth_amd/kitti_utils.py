@@ -61,21 +61,13 @@ def velo_to_image_matrix(cam2cam, velo2cam, cam=2):
     return np.dot(np.dot(P_rect, R_cam2rect), rigid), (H, W)
 
 
-def _gpu(**ts):
-    for name, (t, dtype) in ts.items():
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.WmdError("project_lidar runs on the GPU only (%s is %s)" % (name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-        if t.dtype != dtype:
-            raise _lib.WmdError("%s must be %s (got %s)" % (name, dtype, t.dtype))
-
-
 def project_lidar(points, P, im_shape, vel_depth=False, offsets=None):
     """points [N,4] float32 (the 4th column is ignored), P [3,4] float64 -> depth [H,W] float32; or the packed batch:
     points [total,4], offsets [B+1] int64 on the device (scan b is rows offsets[b] .. offsets[b+1]-1), P [B,3,4] ->
     [B,H,W].  Per pixel the value of the last point that lands there -- the forward coordinate x with vel_depth, else
     the camera depth -- then the reference's duplicate rule over sub2ind buckets; 0 where nothing lands."""
     single = offsets is None
-    _gpu(points=(points, torch.float32), P=(P, torch.float64))
+    _lib.require_device("project_lidar", points=(points, torch.float32), P=(P, torch.float64))
     if points.dim() != 2 or points.shape[1] != 4:
         raise _lib.WmdError("points must be [N,4] (got %s)" % (tuple(points.shape),))
     total = points.shape[0]
@@ -84,7 +76,7 @@ def project_lidar(points, P, im_shape, vel_depth=False, offsets=None):
             raise _lib.WmdError("P must be [3,4] for a single scan (got %s)" % (tuple(P.shape),))
         P = P.unsqueeze(0)
         offsets = torch.tensor([0, total], dtype=torch.int64, device=points.device)
-    _gpu(offsets=(offsets, torch.int64))
+    _lib.require_device("project_lidar", offsets=(offsets, torch.int64))
     if offsets.dim() != 1 or offsets.numel() < 2 or tuple(P.shape) != (offsets.numel() - 1, 3, 4):
         raise _lib.WmdError("offsets must be [B+1] and P [B,3,4] (got %s, %s)" % (tuple(offsets.shape), tuple(P.shape)))
     B = offsets.numel() - 1
@@ -93,8 +85,7 @@ def project_lidar(points, P, im_shape, vel_depth=False, offsets=None):
         raise _lib.WmdError("im_shape must be positive (got %d x %d)" % (H, W))
     points, P, offsets = points.detach().contiguous(), P.detach().contiguous(), offsets.contiguous()
     l = _lib.lib()
-    n = l.wmd_lidar_depth_workspace_bytes(B, H, W)
-    ws = torch.empty(max(n, 8) // 8, device=points.device, dtype=torch.int64)
+    ws, n = _lib.byte_workspace(l.wmd_lidar_depth_workspace_bytes(B, H, W), points.device)
     depth = torch.empty((B, H, W), device=points.device, dtype=torch.float32)
     check(l.wmd_lidar_depth_maps(ptr(points) if total else None, ptr(offsets), ptr(P), total, B, H, W, 1 if vel_depth else 0,
                                  ptr(depth), ptr(ws), n, current_stream()), "wmd_lidar_depth_maps")

@@ -81,14 +81,6 @@ def bicubic_table(n_in, n_out):
     return resample_table(FILTER_BICUBIC, n_in, n_out)
 
 
-def _gpu(who, **ts):
-    for name, t in ts.items():
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.WmdError("%s runs on the GPU only (%s is %s)" % (who, name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-        if t.dtype != torch.uint8:
-            raise _lib.WmdError("%s: %s must be torch.uint8 (got %s): 16-bit depth maps are not implemented" % (who, name, t.dtype))
-
-
 def train_transform(image_u8, depth_u8, aug=None, is_224=False, crop=16, image_size=None, depth_size=None, disparity=False, keep_u8=False):
     """image_u8 uint8 [B,H0,W0,3], depth_u8 uint8 [B,H0,W0] on the device -> {"image": float32 [B,3,ih,iw], "depth": float32
     [B,1,dh,dw]}, plus "disp_gt" = 10 / depth with `disparity` and the uint8 resized planes "image_u8" [B,ih,iw,3] and
@@ -96,7 +88,7 @@ def train_transform(image_u8, depth_u8, aug=None, is_224=False, crop=16, image_s
     (224, 224) for both with is_224.  aug: an Augmentation of B items on the same device; None is getNoTransform: no flip, no
     swap and no table."""
     who = "train_transform"
-    _gpu(who, image_u8=image_u8, depth_u8=depth_u8)
+    _lib.require_device(who, image_u8=(image_u8, torch.uint8), depth_u8=(depth_u8, torch.uint8, "16-bit depth maps are not implemented"))
     if image_u8.dim() != 4 or image_u8.shape[3] != 3:
         raise _lib.WmdError("image_u8 must be [B,H0,W0,3] (got %s)" % (tuple(image_u8.shape),))
     B, H0, W0 = (int(v) for v in image_u8.shape[:3])

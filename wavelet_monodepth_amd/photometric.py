@@ -19,16 +19,6 @@ from . import _lib
 from ._lib import check, current_stream, ptr
 
 
-def _gpu(*ts):
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise _lib.WmdError("the photometric operators run on the GPU only (got a %s tensor)" % t.device)
-        if t.dtype != torch.float32:
-            raise _lib.WmdError("float32 tensors expected (got %s)" % t.dtype)
-
-
 class _SsimFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, mode, w_ssim, w_l1):
@@ -51,7 +41,7 @@ class _SsimFn(torch.autograd.Function):
         dy = torch.empty_like(y) if need_y else None
         if need_x or need_y:
             n = l.wmd_ssim_bwd_workspace_floats(B, Cc, H, W)
-            ws = torch.empty(n, device=x.device, dtype=torch.float32)
+            ws = _lib.float_workspace(n, x.device)
             check(l.wmd_ssim_bwd(ptr(x), ptr(y), ptr(g.contiguous()), ptr(dx), ptr(dy), B, Cc, H, W, mode, w_ssim, w_l1, ptr(ws), n,
                                  current_stream()), "wmd_ssim_bwd")
         return dx, dy, None, None, None
@@ -61,13 +51,13 @@ class SSIM(nn.Module):
     """Layer to compute the SSIM loss between a pair of images: clamp((1 - SSIM(x, y)) / 2, 0, 1), [B,C,H,W]."""
 
     def forward(self, x, y):
-        _gpu(x, y)
+        _lib.require_device("SSIM", x=(x, torch.float32), y=(y, torch.float32))
         return _SsimFn.apply(x, y, 0, 1.0, 0.0)
 
 
 def compute_reprojection_loss(pred, target, use_ssim=True, no_ssim=False):
     """[B,1,H,W]: mean_c |target - pred| when SSIM is off, else 0.85 * mean_c SSIM-loss + 0.15 * mean_c L1."""
-    _gpu(pred, target)
+    _lib.require_device("compute_reprojection_loss", pred=(pred, torch.float32), target=(target, torch.float32))
     if no_ssim or not use_ssim:
         return _SsimFn.apply(pred, target, 1, 0.0, 1.0)
     return _SsimFn.apply(pred, target, 1, 0.85, 0.15)
@@ -98,7 +88,7 @@ class _WarpFn(torch.autograd.Function):
         ddepth = torch.empty_like(depth)
         dT = torch.empty_like(T)
         n = l.wmd_warp_bwd_workspace_floats(C.byref(a))
-        ws = torch.empty(n, device=color.device, dtype=torch.float32)
+        ws = _lib.float_workspace(n, color.device)
         check(l.wmd_warp_bwd(C.byref(a), ptr(g.contiguous()), ptr(ddepth), ptr(dT), ptr(ws), n, current_stream()), "wmd_warp_bwd")
         return None, ddepth, None, None, dT, None
 
@@ -106,7 +96,7 @@ class _WarpFn(torch.autograd.Function):
 def warp_frame(color, depth, K, inv_K, T, eps=1e-7):
     """color [B,C,Hs,Ws] source frame, depth [B,1,H,W], K / inv_K / T [B,4,4] -> the source frame resampled into the target
     view [B,C,H,W].  Differentiable w.r.t. depth and T (the colour frame and the intrinsics are constants of the loss)."""
-    _gpu(color, depth, K, inv_K, T)
+    _lib.require_device("warp_frame", **{k: (v, torch.float32) for k, v in (("color", color), ("depth", depth), ("K", K), ("inv_K", inv_K), ("T", T))})
     if color.requires_grad or K.requires_grad or inv_K.requires_grad:
         raise _lib.WmdError("warp_frame differentiates w.r.t. depth and T only")
     return _WarpFn.apply(color, depth, K, inv_K, T, eps)
@@ -119,7 +109,7 @@ class _SmoothFn(torch.autograd.Function):
         B, _, H, W = disp.shape
         l = _lib.lib()
         n = l.wmd_smooth_workspace_floats(B, H, W)
-        ws = torch.empty(n, device=disp.device, dtype=torch.float32)
+        ws = _lib.float_workspace(n, disp.device)
         out = torch.empty(1, device=disp.device, dtype=torch.float32)
         check(l.wmd_smooth_fwd(ptr(disp), ptr(img), ptr(out), B, img.shape[1], H, W, float(gamma), ptr(ws), n, current_stream()),
               "wmd_smooth_fwd")
@@ -139,7 +129,7 @@ class _SmoothFn(torch.autograd.Function):
 
 def get_smooth_loss(disp, img, gamma=2):
     """Edge-aware smoothness of a (mean-normalised) disparity map; scalar tensor, differentiable w.r.t. disp."""
-    _gpu(disp, img)
+    _lib.require_device("get_smooth_loss", disp=(disp, torch.float32), img=(img, torch.float32))
     if disp.shape[1] != 1:
         raise _lib.WmdError("disp must be [B,1,H,W]")
     return _SmoothFn.apply(disp, img, gamma)

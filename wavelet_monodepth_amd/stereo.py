@@ -48,11 +48,7 @@ def reference_settings():
 
 
 def _images(who, left, right):
-    for name, t in (("left", left), ("right", right)):
-        if not t.is_cuda:
-            raise _lib.WmdError("%s runs on the GPU only (%s is a %s tensor)" % (who, name, t.device))
-        if t.dtype != torch.uint8:
-            raise _lib.WmdError("%s: %s must be uint8 (got %s)" % (who, name, t.dtype))
+    _lib.require_device(who, left=(left, torch.uint8), right=(right, torch.uint8))
     if left.dim() == 3:
         left, right = left.unsqueeze(-1), right.unsqueeze(-1)
     if left.dim() != 4 or left.shape != right.shape or left.device != right.device:
@@ -84,8 +80,7 @@ def sgbm(left_u8, right_u8, settings, reverse=None, return_volumes=False):
     dev = left.device
     rev = _reverse(who, reverse, B, dev)
     l = _lib.lib()
-    n_ws = l.wmd_stereo_sgbm_workspace_bytes(B, H, W, C, s.minDisparity, s.numDisparities, s.blockSize)
-    ws = torch.empty(max(n_ws, 256) // 8, device=dev, dtype=torch.int64)
+    ws, n_ws = _lib.byte_workspace(l.wmd_stereo_sgbm_workspace_bytes(B, H, W, C, s.minDisparity, s.numDisparities, s.blockSize), dev)
     disp = torch.empty((B, H, W), device=dev, dtype=torch.int16)
     cost = vol = None
     if return_volumes:
@@ -102,16 +97,14 @@ def sgbm(left_u8, right_u8, settings, reverse=None, return_volumes=False):
 def filter_speckles(disp_i16, invalid, max_size, max_diff):
     """int16 [B,H,W] (or [H,W]) -> a copy in which every 4-connected component of at most max_size pixels is `invalid`;
     neighbours belong together when both differ from `invalid` and from each other by at most max_diff (int16 units)."""
-    if not disp_i16.is_cuda:
-        raise _lib.WmdError("filter_speckles runs on the GPU only (got a %s tensor)" % disp_i16.device)
-    if disp_i16.dtype != torch.int16 or disp_i16.dim() not in (2, 3):
-        raise _lib.WmdError("filter_speckles: int16 [B,H,W] or [H,W] expected (got %s %s)" % (disp_i16.dtype, tuple(disp_i16.shape)))
+    _lib.require_device("filter_speckles", disp_i16=(disp_i16, torch.int16))
+    if disp_i16.dim() not in (2, 3):
+        raise _lib.WmdError("filter_speckles: int16 [B,H,W] or [H,W] expected (got %s)" % (tuple(disp_i16.shape),))
     out = disp_i16.contiguous().clone()
     H, W = (int(v) for v in out.shape[-2:])
     B = int(out.shape[0]) if out.dim() == 3 else 1
     l = _lib.lib()
-    n_ws = l.wmd_stereo_filter_speckles_workspace_bytes(B, H, W)
-    ws = torch.empty(max(n_ws, 8) // 8, device=out.device, dtype=torch.int64)
+    ws, n_ws = _lib.byte_workspace(l.wmd_stereo_filter_speckles_workspace_bytes(B, H, W), out.device)
     check(l.wmd_stereo_filter_speckles(ptr(out), B, H, W, int(invalid), int(max_size), int(max_diff), ptr(ws), n_ws, current_stream()),
           "wmd_stereo_filter_speckles")
     return out

@@ -40,16 +40,9 @@ def colormap(name, device=None):
     return _device_tables[key]
 
 
-def _gpu(t, what):
-    if not t.is_cuda:
-        raise _lib.WmdError("%s runs on the GPU only (got a %s tensor)" % (what, t.device))
-    if t.dtype != torch.float32:
-        raise _lib.WmdError("%s expects a float32 tensor (got %s)" % (what, t.dtype))
-    return t.contiguous()
-
-
 def _maps(t, what):
-    """[H,W], [B,H,W] or [B,1,H,W] -> [B,H,W]"""
+    """a float32 device tensor [H,W], [B,H,W] or [B,1,H,W] -> [B,H,W]"""
+    _lib.require_device(what, input=(t, torch.float32))
     if t.dim() == 2:
         return t[None]
     if t.dim() == 4 and t.shape[1] == 1:
@@ -59,20 +52,15 @@ def _maps(t, what):
     return t
 
 
-def _workspace(B, H, W, dev):
-    n = _lib.lib().wmd_viz_workspace_bytes(B, H, W)
-    return torch.empty((n + 3) // 4, device=dev, dtype=torch.int32), n
-
-
 def disparity_image(disp, size=None, percentile=95, cmap="magma", return_range=False, return_resized=False, workspace=None):
     """disp [B,h,w] (or [B,1,h,w], [h,w]) float32 at decoder resolution -> uint8 [B,H,W,3] on the device: what test_simple
     saves as <name>_disp.jpeg, for every image of the batch in five launches.  size = (H, W) of the pictures (None: h, w).
     vmin = the map's min, vmax = np.percentile(map, percentile) exactly (a radix select, no sort), per image.
     return_range: also [B,2] float32 (vmin, vmax); return_resized: also the resized maps [B,H,W], bit-equal to
-    ops.upsample_bilinear(disp, size).  workspace: an int32 tensor to reuse between calls (its contents do not matter)."""
+    ops.upsample_bilinear(disp, size).  workspace: a device tensor of any dtype to reuse between calls (its contents do not matter)."""
     if not 0 <= float(percentile) <= 100:
         raise ValueError("Percentiles must be in the range [0, 100]")
-    d = _maps(_gpu(disp, "disparity_image"), "disparity_image").contiguous()
+    d = _maps(disp, "disparity_image").contiguous()
     B, h, w = d.shape
     H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
     dev = d.device
@@ -81,7 +69,7 @@ def disparity_image(disp, size=None, percentile=95, cmap="magma", return_range=F
     res = torch.empty((B, H, W), device=dev, dtype=torch.float32) if return_resized else None
     l = _lib.lib()
     if workspace is None:
-        workspace, n = _workspace(B, H, W, dev)
+        workspace, n = _lib.byte_workspace(l.wmd_viz_workspace_bytes(B, H, W), dev)
     else:
         n = workspace.numel() * workspace.element_size()
     check(l.wmd_viz_disparity(ptr(d), B, h, w, H, W, float(percentile), ptr(colormap(cmap, dev)), ptr(rgb), ptr(res), ptr(rng),
@@ -96,12 +84,12 @@ def colorize(value, vmin=0.1, vmax=10, cmap="plasma", channels_first=True):
     colour, above -> the last, NaN -> black.  Both None: every map's own min and max.  One of the two None: ValueError."""
     if (vmin is None) != (vmax is None):
         raise ValueError("colorize: give both vmin and vmax, or neither")
-    v = _maps(_gpu(value, "colorize"), "colorize").contiguous()
+    v = _maps(value, "colorize").contiguous()
     B, H, W = v.shape
     dev = v.device
     out = torch.empty((B, 3, H, W) if channels_first else (B, H, W, 3), device=dev, dtype=torch.uint8)
     auto = vmin is None
-    ws, n = _workspace(B, 1, 1, dev) if auto else (None, 0)
+    ws, n = _lib.byte_workspace(_lib.lib().wmd_viz_workspace_bytes(B, 1, 1), dev) if auto else (None, 0)
     # as numpy does with a float32 array and Python scalars: the difference in double, each scalar rounded to float32
     lo, den = (0.0, 0.0) if auto else (float(np.float32(vmin)), float(np.float32(vmax - vmin)))
     check(_lib.lib().wmd_viz_colorize(ptr(v), B, H * W, int(auto), lo, den, ptr(colormap(cmap, dev)), ptr(out), int(bool(channels_first)),
@@ -112,11 +100,12 @@ def colorize(value, vmin=0.1, vmax=10, cmap="plasma", channels_first=True):
 def normalize_image(x, per_image=False):
     """(x - min) / (max - min) in float32, 1e5 in place of a zero range; the range over the whole tensor (the reference's
     form) or, per_image, over every x[b] on its own.  Same shape as x."""
-    v = _gpu(x, "normalize_image")
+    _lib.require_device("normalize_image", x=(x, torch.float32))
+    v = x.contiguous()
     if v.numel() == 0:
         return v.clone()
     B = v.shape[0] if per_image and v.dim() > 1 else 1
     y = torch.empty_like(v)
-    ws, n = _workspace(B, 1, 1, v.device)
+    ws, n = _lib.byte_workspace(_lib.lib().wmd_viz_workspace_bytes(B, 1, 1), v.device)
     check(_lib.lib().wmd_viz_normalize(ptr(v), ptr(y), B, v.numel() // B, ptr(ws), n, current_stream()), "wmd_viz_normalize")
     return y
